@@ -17,13 +17,19 @@ with hiprtc before the warmup (compile time reported as config.jit_compile_ms,
 outside the timed region, like the plan), then every timed step walks all
 2^39 Gray steps.  --jit -1 runs the ahead-of-time prefix-blocked kernel.
 
+A plain run does only that: plan, warm up, time --steps steps, print ONE JSON
+line on rank 0 (driver contract) with the headline figure.  --dump-outputs DIR
+also writes what the last timed step returned (DIR/permanent.npy, float64; the
+input is a committed file, so two builds can be compared value for value).
+Everything below runs only with --full, and is added to the same line.
+
 The north star also asks for density 0.2: the reference corpus matrix
 double/40_0.20_0 (--also) is timed the same way (same shards, all-reduce and
 clock) and reported under "densities"; `value` stays the d = 0.5 metric.
 BASELINE configs 2, 3 and 5 are timed the same way under "configs"
 (--configs 0 skips them).
 
-Prints ONE JSON line on rank 0 (driver contract), including the roofline of
+With --full the line includes the roofline of
 the walk kernel and a CPU baseline (oracle/ port of the reference's
 parallel_perman64 chunk loop, timed on a bounded sample of the same workload
 on this host's cores; beside it the reference's own compiled CPU code on
@@ -57,6 +63,14 @@ def parse():
                          "starts torch.distributed.run with N ranks as a child and forwards its output")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: companion densities (--also), BASELINE "
+                         "configs (--configs), the roofline (--pmc), errors against the exact and the reference's "
+                         "results, the CPU baselines (--cpu-seconds) and the CLI's cold start (--cold); those "
+                         "options have no effect without --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/permanent.npy "
+                         "(float64, shape (1,); rank 0)")
     ap.add_argument("--matrix", default=os.path.join(ROOT, "tests", "fixtures", "double__40_0.50_0"))
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU-baseline sample budget (0 = skip)")
     ap.add_argument("--kernel", default="dense", choices=["dense", "dense_plain", "dense_lds", "sparse", "skip", "seg"],
@@ -436,6 +450,8 @@ def main():
     args = parse()
     if args.pmc_child:
         return pmc_child(args)
+    if not args.full:  # a plain run times the headline only: no companion, config, counter, CPU or CLI leg
+        args.also, args.configs, args.pmc, args.cpu_seconds, args.cold = "", 0, 0, 0.0, 0
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and (args.gpus or 1) > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -667,10 +683,6 @@ def main():
 
     total_steps = args.steps * (1 << (n - 1))
     value = total_steps / elapsed
-    roof = roofline(args.matrix, a, args.prep, args.kernel, args.jit, k_ms, st)
-    walk = roof["kernel"]
-    pmc = pmc_record(n, walk, roof["plan_key"])
-    roof["traffic"] = hbm_traffic(pmc)
     fname = os.path.basename(args.matrix).replace("__", "/")
     density = float((a != 0).sum()) / (n * n)
     rec = {
@@ -693,14 +705,26 @@ def main():
                    "walk": walk_names[st["walk_kind"]],
                    "jit_compile_ms": compile_ms,
                    "parallelism": f"dp{world}: contiguous wave-chunk shards + one RCCL all-reduce"},
-        "roofline": roof,
         "permanent": perm,
         "kernel_ms_per_rank": rank_kms,
         "plan_keys_per_rank": plan_keys[0],
         "process_group": dist.get_backend() if use_pg else None,
-        "densities": also,
-        "configs": configs,
     }
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "permanent.npy"), np.array([perm], dtype=np.float64))
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(rec), flush=True)
+        if use_pg:
+            dist.destroy_process_group()
+        return
+    roof = roofline(args.matrix, a, args.prep, args.kernel, args.jit, k_ms, st)
+    walk = roof["kernel"]
+    pmc = pmc_record(n, walk, roof["plan_key"])
+    roof["traffic"] = hbm_traffic(pmc)
+    rec.update(roofline=roof, densities=also, configs=configs)
     if pmc:  # rocprofv3 HBM evidence for the dominant kernel (committed profile of the same plan)
         alg = pmc.get("algorithmic_bytes_per_launch")
         rec["roofline"].update({

@@ -25,7 +25,7 @@ from conftest import ROOT, fixture_path
 
 pytestmark = pytest.mark.gpu
 
-_QUICK = ["--steps", "1", "--warmup", "1", "--cpu-seconds", "0", "--pmc", "0", "--cold", "0", "--also", ""]
+_QUICK = ["--full", "--steps", "1", "--warmup", "1", "--cpu-seconds", "0", "--pmc", "0", "--cold", "0", "--also", ""]
 
 
 def _free_port() -> int:

@@ -29,7 +29,7 @@ for step in "$@"; do
     smoke) run smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()";;
     test)  run pytest_gpu 1200 python3 -m pytest tests -m gpu -q -x -p no:cacheprovider;;
     testall) run pytest_gpu 1200 python3 -m pytest tests -m gpu -q -p no:cacheprovider;;
-    bench) run bench 600 python3 bench.py --steps 3 --warmup 1;;
+    bench) run bench 600 python3 bench.py --full --steps 3 --warmup 1;;
     prof)  run prof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python3 bench.py --steps 3 --warmup 1 --cpu-seconds 0 --also= --configs 0 ${BENCH_EXTRA:-};;
     list)  run counters 120 rocprofv3 -L;;
     pmc)   prof_pmc pmc_fetch FETCH_SIZE

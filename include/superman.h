@@ -170,11 +170,13 @@ uint64_t    sup_device_checks(void);
  * caller can run it on a thread beside its planning (the perman CLI does).
  * Thread-safe; a later call on the same devices returns at once. */
 int         sup_device_warmup(int device_id, int gpu_num, int n);
-/* The walk-kernel times (HIP events on the walk's stream) of this thread's
- * sup_perman_shard calls on logical device `device_id` made with
- * sup_opts.timing = 0 since the last sup_kernel_time: waits for them, returns
- * their sum (*total_ms) and count (*launches), and starts a new tally.  Any
- * pointer may be NULL (the tally is still reset). */
+/* The walk-kernel times (HIP events on the walk's stream) of the
+ * sup_perman_shard calls made with sup_opts.timing = 0 on the calling thread's
+ * context — logical device `device_id` and the thread's context lane — since
+ * the last sup_kernel_time there: waits for them, returns their sum
+ * (*total_ms) and count (*launches), and starts a new tally.  The tally
+ * belongs to the context, not the thread: threads that share a device and
+ * lane share it.  Any pointer may be NULL (the tally is still reset). */
 int         sup_kernel_time(int device_id, double* total_ms, uint64_t* launches);
 
 /* ------------------------------------------------------------------------ *

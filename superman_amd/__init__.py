@@ -117,7 +117,7 @@ def layout(n: int) -> tuple[int, int, int]:
     L = min(6, nb)
     rest = nb - L
     m = min(rest, 10)
-    if rest - m < 13:  # small n: shorter walks, 2^13 wave-chunks (engine.cpp default_layout)
+    if rest - m < 13:  # small n: shorter walks, 2^13 wave-chunks (plan.cpp default_layout)
         m = max(min(rest, 6), rest - 13)
     m = min(max(m, rest - 20), 31)
     return L, m, rest - m

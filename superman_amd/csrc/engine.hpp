@@ -1,6 +1,6 @@
-// engine.hpp — host side of the MI355X permanent engine: plans, device
-// contexts, schedulers.  Replaces the reference's per-call wrappers
-// (gpu_exact_dense.cu:401-990, gpu_exact_sparse.cu:673-1408), which recompute
+// engine.hpp — host side of the MI355X permanent engine: plans (plan.cpp),
+// device contexts (engine.cpp), schedulers (schedule.cpp).  Replaces the
+// reference's per-call wrappers (gpu_exact_dense.cu:401-990, gpu_exact_sparse.cu:673-1408), which recompute
 // x0/transpose, cudaMalloc, launch, D2H 2-4 MiB of per-thread partials and sum
 // on the host on every call.
 #pragma once
@@ -20,6 +20,9 @@ namespace sup {
 // Thread-local error channel behind sup_last_error().
 void set_error(const std::string& msg);
 const char* last_error();
+// An on/off environment knob: atoi(value) != 0, `dflt` when unset.  A knob read
+// once per process keeps the answer in a function-local static.
+bool env_on(const char* name, bool dflt);
 
 // Convert the caller's T matrix (int/float/double) to fp64 (exact for all three).
 int to_double(const void* mat, sup_dtype t, int n, std::vector<double>& out);
@@ -144,13 +147,13 @@ int make_plan(const double* A, int n, WalkKind kind, bool identity_map, const La
 // Walk-column order minimising the prefix-block cost (first `count` columns).
 std::vector<int> greedy_walk_order(const double* A, int n, int count);
 // SkipPer walk + lane columns (walk first) chosen for the chunks its first-state
-// zero check ends (integer matrices); false: keep SkipOrder's map (engine.cpp).
+// zero check ends (integer matrices); false: keep SkipOrder's map (plan.cpp).
 // baseline (m + L columns; NULL: SkipOrder's map) is kept unless the search beats
 // its ops x chunks walked by `factor`.
 bool skip_walk_order(const double* A, int n, const Layout& lay, std::vector<int>& out,
                      const std::vector<int>* baseline, double factor);
 // A long prefix-blocked plan of an integer matrix, its columns searched for
-// chunk ends (engine.cpp; exact.cpp and quad.cpp use it too).
+// chunk ends (plan.cpp; exact.cpp and quad.cpp use it too).
 int improve_sparse_plan(const double* A, int n, const Layout& lay, Plan& P);
 // Host threads the planners' searches use (jit.cpp).
 int plan_threads();
@@ -236,6 +239,10 @@ double jit_compile_ms_thread();
 // Estimated fp64 VALU ops per Gray step of a plan (dense: 2n+1; prefix kernels:
 // sum_k 2^-(k+1) (16 nblk_k + 1)).
 double walk_cost(const Plan& P);
+// Predicted seconds of `steps` Gray steps of P on one MI355X: steps x the
+// plan's ops per nominal step (skipped chunks discounted) / the walk kernels'
+// measured lane-op rate (plan.cpp; run_range's spin-or-block prediction).
+double walk_seconds(const Plan& P, double steps);
 
 // The plan sup_perman / sup_perman_shard run for this request: for
 // SUP_KERNEL_DENSE the engine takes the prefix-blocked walk whenever its cost
@@ -260,19 +267,32 @@ struct RangeResult {
   double compile_ms = 0.0;  // segmented walk: hiprtc compile time spent by this call
 };
 
-// Walk wave-chunks [c0, c1) of plan P on device `dev` (synchronous).
 // The dynamic item queue shared by -p6/-p8, the exact path and the
-// estimators: `takers` host threads (one per device, plus the hybrid CPU
-// worker) pull item indices 0..nitems-1 from one atomic counter until they run
-// out or a taker fails; take(taker, item) writes only its own outputs
-// (item-indexed slots, per-taker accumulators), so the combined result never
-// depends on who took which item.  Returns SUP_OK or the first failure (with
-// its message).
+// estimators (schedule.cpp): `takers` host threads (one per device, plus the
+// hybrid CPU worker) pull item indices 0..nitems-1 from one atomic counter
+// until they run out or a taker fails; take(taker, item) writes only its own
+// outputs (item-indexed slots, per-taker accumulators), so the combined result
+// never depends on who took which item.  Returns SUP_OK or the first failure
+// (with its message).
 int run_item_queue(uint64_t nitems, int takers, const std::function<int(int, uint64_t)>& take);
+// Walk wave-chunks [c0, c1) of plan P on device `dev` (synchronous).
 // slot (optional): a device pointer on `dev`; the range's partial is also
 // copied there on the device (the -R combine all-reduces those slots).
 int run_range(int dev, const Plan& P, uint64_t c0, uint64_t c1, bool want_visited, RangeResult& r,
               double* slot = nullptr);
+// Launch geometry of a walk over `count` wave-chunks on `resident_blocks`
+// resident blocks of `waves_per_block` waves (engine.cpp; pure, so the host
+// self-test pins it): the chunk group a ticket hands out, the segmented
+// walk's tail phase (tail_group 0 and tail_ticket 0xffffffff: none) and the
+// grid.  force_group > 0 / force_tail >= 0: the SUP_WALK_GROUP / SUP_WALK_TAIL
+// experiment overrides; group_cap: a leaf batch's group stays within one leaf.
+struct LaunchGeom {
+  unsigned group, tail_group;
+  uint64_t tail_begin, grid;
+  unsigned tail_ticket;
+};
+LaunchGeom walk_geometry(uint64_t count, uint64_t resident_blocks, uint64_t waves_per_block, bool seg,
+                         int force_group = 0, int force_tail = -1, uint64_t group_cap = 64);
 // Leaf batches (sup_perman_reduced's leaves): up to kMaxBatchLeaves plans of
 // one order, walk kind (plain / prefix-blocked) and layout in one launch on
 // device `dev`; partial[i] is bit-identical to run_range over plan i's whole
@@ -349,7 +369,7 @@ struct SchedResult {
 };
 int schedule(const Plan& P, sup_sched sched, const sup_opts& o, uint64_t c0, uint64_t c1,
              SchedResult& out);
-// Checkpoint file of the chunk queue (sup_opts::checkpoint; engine.cpp):
+// Checkpoint file of the chunk queue (sup_opts::checkpoint; schedule.cpp):
 // ckpt_open loads the items a file with header `head` records (marking them
 // in `done`, their partials in `ipart`) and leaves it open for appending;
 // ckpt_record appends one finished item (thread-safe, flushed and fsynced).

@@ -91,7 +91,7 @@ static void test_queue() {
 }
 
 // Checkpoint file of the chunk queue: concurrent appends, reload, a torn last
-// line dropped, a foreign header refused (engine.cpp ckpt_open / ckpt_record).
+// line dropped, a foreign header refused (schedule.cpp ckpt_open / ckpt_record).
 static void test_checkpoint() {
   char path[] = "/tmp/sup_selftest_ckpt_XXXXXX";
   const int fd = mkstemp(path);
@@ -142,6 +142,51 @@ static void test_checkpoint() {
           SUP_EINVAL);
   }
   std::remove(path);
+}
+
+// Launch geometry (walk_geometry, engine.cpp: what run_range and
+// run_range_batch hand the kernels), 4 waves per block: its invariants over a
+// sweep, and cases worked out by hand.
+static void test_launch_geometry() {
+  auto pow2 = [](uint64_t v) { return v != 0 && (v & (v - 1)) == 0; };
+  std::vector<uint64_t> counts{3, 63, 65, 1000, 4097, 99999, 1000003, (1ull << 20) - 1};
+  for (int b = 0; b <= 20; ++b) counts.push_back(1ull << b);
+  for (uint64_t count : counts)
+    for (uint64_t resident : {4, 16, 512})
+      for (bool seg : {false, true}) {
+        const sup::LaunchGeom g = sup::walk_geometry(count, resident, 4, seg);
+        CHECK(pow2(g.group) && g.group <= 64);
+        CHECK(g.tail_group == 0 || (pow2(g.tail_group) && g.tail_group <= g.group));
+        CHECK(g.tail_begin <= count && (g.tail_begin == count || g.tail_begin % 64 == 0));
+        CHECK(g.grid >= 1 && g.grid <= resident);
+        CHECK(g.tail_ticket == (g.tail_group ? (unsigned)(g.tail_begin / g.group) : 0xffffffffu));
+        CHECK(seg || g.tail_group == 0);
+      }
+  struct Case {
+    bool seg;
+    uint64_t count, resident;
+    int force_group, force_tail;
+    unsigned group, tail_group;
+    uint64_t tail_begin;
+    unsigned tail_ticket;
+    uint64_t grid;
+  };
+  const Case cases[] = {
+      {true, 1ull << 20, 512, 0, -1, 16, 4, 983040, 61440, 512},
+      {false, 1ull << 20, 512, 0, -1, 16, 0, 1ull << 20, 0xffffffffu, 512},
+      {true, 1, 512, 0, -1, 1, 0, 1, 0xffffffffu, 1},
+      {true, 8192, 512, 0, -1, 1, 0, 8192, 0xffffffffu, 512},
+      {true, 65536, 16, 0, -1, 32, 8, 61440, 1920, 16},
+      {true, 2048, 512, 16, -1, 16, 4, 0, 0, 32},
+      {true, 1ull << 20, 512, 0, 0, 16, 0, 1ull << 20, 0xffffffffu, 512},
+  };
+  for (const Case& k : cases) {
+    const sup::LaunchGeom g = sup::walk_geometry(k.count, k.resident, 4, k.seg, k.force_group, k.force_tail);
+    CHECK(g.group == k.group && g.tail_group == k.tail_group && g.tail_begin == k.tail_begin &&
+          g.tail_ticket == k.tail_ticket && g.grid == k.grid);
+  }
+  // a leaf batch's cap: the group stays within one leaf's chunks
+  CHECK(sup::walk_geometry(1ull << 20, 512, 4, false, 0, -1, 8).group == 8);
 }
 
 static void test_host_walks() {
@@ -351,6 +396,7 @@ int main(int argc, char** argv) {
   const std::string root = argc > 1 ? argv[1] : ".";
   test_queue();
   test_checkpoint();
+  test_launch_geometry();
   test_host_walks();
   test_planning(root);
   test_io_and_reductions(root);

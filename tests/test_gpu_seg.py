@@ -144,7 +144,7 @@ def test_seg_n40_d02_companion(sup):
     b = a.copy()
     b[7] *= 4.0
     assert sup.perman(b, algo=4, jit=1) == r_seg * 4.0
-    # cheap steps: the plan lengthens the wave-chunks (engine.cpp make_seg_plan);
+    # cheap steps: the plan lengthens the wave-chunks (plan.cpp make_seg_plan);
     # the shards of that layout still pair up to the full sum bit for bit
     assert sup.plan_info(a, "dense", jit=1)["m"] > sup.layout(40)[1]
     full = sup.perman_shard(a, 0, 1, jit=1)

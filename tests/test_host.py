@@ -130,7 +130,7 @@ def test_config5_fixtures_reproducible(sup, tmp_path):
 
 
 def test_skipper_column_search(sup):
-    """SkipPer's column map for long integer walks (engine.cpp
+    """SkipPer's column map for long integer walks (plan.cpp
     skip_walk_order): config 5 takes a searched map, the same in every process
     (the plan must not depend on the host or the device count), with a lower
     prefix cost than SkipOrder's map; a non-integer matrix and a short walk keep

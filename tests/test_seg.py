@@ -276,7 +276,7 @@ def test_seg_pair_bits_chosen_by_cost(sup, monkeypatch):
 
 
 def test_seg_walk_length_rule(sup):
-    """Cheap segmented walks run on longer wave-chunks (engine.cpp
+    """Cheap segmented walks run on longer wave-chunks (plan.cpp
     make_seg_plan): a chunk's walk should cost >= 32 chunk starts, with at
     least 2^14 chunks left (2^15 until round 6).  Measured on MI355X
     (profiles/r2/probe_walklen.log, profiles/r6/cfg2_knobs.log, cfg3_m.log):

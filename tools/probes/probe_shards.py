@@ -12,7 +12,7 @@ import superman_amd as S  # noqa: E402
 
 # the n = 40 headline, and config 5 (n = 44 d = 0.15 int, -p8 -s -r2: the
 # segmented walk skips 87 % of its wave-chunks; the planner's column order
-# keeps the shards' skip patterns equal, engine.cpp make_plan)
+# keeps the shards' skip patterns equal, plan.cpp make_plan)
 cases = [("dense n=40 d=0.5 (bench)", S.read_matrix(os.path.join(ROOT, "tests", "fixtures", "double__40_0.50_0"))[0],
           "dense"),
          ("config 2 n=32 d=0.5", S.read_matrix(os.path.join(ROOT, "tests", "fixtures", "double__32_0.50_0"))[0], "dense"),

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SUP_ABI_VERSION 10  /* 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
+#define SUP_ABI_VERSION 11  /* 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SUP_OK            0
@@ -275,6 +275,33 @@ int sup_perman_exact(const void* mat, sup_dtype t, int n, const sup_opts* o, int
 int sup_perman_quad(const void* mat, sup_dtype t, int n, const sup_opts* o, int on_cpu, double* out_hi,
                     double* out_lo, sup_stats* st);
 
+/* The permanent of a complex fp64 matrix (ABI 11).  The reference refuses
+ * complex input (revised_perman/main.cpp:1557); boson-sampling amplitudes are
+ * permanents of dense complex submatrices of unitaries.
+ * mat: n x n row-major, interleaved (re, im) doubles: 2 n^2 doubles; n in
+ * [1, 64].  The dense Ryser / Gray walk of sup_perman (default layout, or
+ * o->walk_log2 walk bits when non-zero; same wave-chunks) with every value a
+ * complex fp64 pair (walk_cplx.hip): 6n - 2 fp64 ops per Gray step, ~3x the
+ * fp64 walk.  o->gpu_num devices from o->device_id split the wave-chunks
+ * statically; on_cpu = 1 runs the same operations in the same order on
+ * o->threads host threads.  Chunk partials are combined in one fixed pairwise
+ * tree over the chunk index, so the result is a function of (matrix, walk
+ * bits) only: bit-identical for any device count, split or thread count.
+ * Non-finite input propagates.  No device with on_cpu = 0: SUP_ENODEV (no
+ * silent CPU fallback).  st: kernel_ms, wall_ms, gray_steps, devices_used,
+ * lane_bits, walk_bits, grid, est_ops_per_step = 6n. */
+int sup_perman_complex(const double* mat, int n, const sup_opts* o, int on_cpu,
+                       double* out_re, double* out_im, sup_stats* st);
+/* The part of the sum from wave-chunks [c0, c1) of the plan (o->walk_log2
+ * honoured; the plan has 2^(n-1-lane_bits-walk_bits) chunks), folded by the
+ * pairwise tree over c - c0, NOT scaled by 4(n&1)-2.
+ * Aligned power-of-two ranges folded pairwise in order reproduce
+ * sup_perman_complex's bits.  One device (o->device_id) or host threads.
+ * c0 > c1 or c1 beyond the plan's chunks: SUP_EINVAL. */
+int sup_perman_complex_range(const double* mat, int n, uint64_t c0, uint64_t c1,
+                             const sup_opts* o, int on_cpu,
+                             double* out_re, double* out_im, sup_stats* st);
+
 /* Nijenhuis-Wilf prologue (gpu_exact_dense.cu:642-652): x0[j] = a[j][n-1] - rowsum_j/2,
  * p0 = prod x0.  Host-only helper, exported for the test harness. */
 int sup_nw_start(const void* mat, sup_dtype t, int n, double* x0, double* p0);
@@ -359,6 +386,14 @@ int sup_skip_order(void* mat, sup_dtype t, int n, int* rowperm, int* colperm);
  * sup_read_matrix also accepts MatrixMarket files (detected by the banner),
  * so the CLI's -f takes either format. */
 int sup_read_mtx(const char* path, int binary, void** mat, sup_dtype* t, int* n, int* nnz_lines);
+/* MatrixMarket coordinate file whose field is `complex`: "i j re im" entries
+ * (ABI 11).  *mat: n x n row-major interleaved (re, im) doubles (sup_free).
+ * general: as written; symmetric: off-diagonal entries mirrored with the same
+ * value; hermitian: mirrored with the conjugate, and a diagonal entry's
+ * imaginary part must be 0.  skew-symmetric, other fields, array format,
+ * non-square, truncated or out-of-range entries: SUP_EIO.  Later duplicates
+ * win.  n up to SUP_MAX_N only (there are no complex reductions). */
+int sup_read_mtx_complex(const char* path, double** mat, int* n, int* nnz_lines);
 
 /* ------------------------------------------------------------------------ *
  * Reductions in front of the engine (reference v2

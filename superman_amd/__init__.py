@@ -20,7 +20,7 @@ from ._lib import (KERNEL_DENSE, KERNEL_SKIPPER, KERNEL_SPARYSER, LEAF_FN, SCHED
                    SCHED_STATIC, SupApproxResult, SupError, SupOpts, SupReduceOpts, SupStats)
 
 __all__ = [
-    "perman", "perman_cpu", "partial", "perman_shard", "plan_info", "plan_key", "prepare", "read_matrix", "read_mtx", "sort_order",
+    "perman", "perman_cpu", "perman_complex", "perman_complex_range", "read_mtx_complex", "partial", "perman_shard", "plan_info", "plan_key", "prepare", "read_matrix", "read_mtx", "sort_order",
     "skip_order", "compress", "decompose", "perman_reduced", "approx", "grid_graph", "ALGOS_APPROX",
     "nw_start", "device_count", "rccl_devices", "layout", "ShardCall", "SupError", "ALGOS_DENSE", "ALGOS_SPARSE",
     "gpu_perman64_xshared_coalescing_mshared",
@@ -197,6 +197,50 @@ def perman_quad(mat, gpu_num: int = 1, device_id: int = 0, cpu: bool = False, th
     _lib.check(lib.sup_perman_quad(a.ctypes.data, dt, n, C.byref(o), int(bool(cpu)), C.byref(hi), C.byref(lo),
                                    C.byref(st)), "perman_quad")
     return ((hi.value, lo.value), st.as_dict()) if return_stats else (hi.value, lo.value)
+
+
+def _cmat(mat) -> tuple[np.ndarray, int]:
+    a = np.ascontiguousarray(np.asarray(mat, dtype=np.complex128))
+    if a.ndim != 2 or a.shape[0] != a.shape[1]:
+        raise ValueError(f"expected a square matrix, got shape {a.shape}")
+    n = a.shape[0]
+    if not 1 <= n <= 64:
+        raise ValueError(f"n = {n} outside [1, 64] (64-bit Gray index)")
+    return a, n  # complex128, C order: interleaved (re, im) doubles
+
+
+def perman_complex(mat, gpu_num: int = 1, device_id: int = 0, cpu: bool = False, threads: int = 16,
+                   walk_log2: int = 0, return_stats: bool = False):
+    """The permanent of a complex matrix (anything np.asarray(..., dtype=complex128)
+    accepts; real input gets a zero imaginary part) as a Python complex: the
+    dense Ryser / Gray walk with complex fp64 values (walk_cplx.hip) on gpu_num
+    devices, or (cpu=True) its host twin on `threads` threads — bit-identical
+    either way, for any device or thread count.  ``walk_log2``: walk bits (0 =
+    default layout); the result is a function of (matrix, walk bits) only."""
+    a, n = _cmat(mat)
+    lib = _lib.load()
+    o = _opts(gpu_num=gpu_num, device_id=device_id, threads=threads, walk_log2=walk_log2)
+    re, im, st = C.c_double(0.0), C.c_double(0.0), SupStats()
+    _lib.check(lib.sup_perman_complex(a.ctypes.data, n, C.byref(o), int(bool(cpu)), C.byref(re), C.byref(im),
+                                      C.byref(st)), "perman_complex")
+    v = complex(re.value, im.value)
+    return (v, st.as_dict()) if return_stats else v
+
+
+def perman_complex_range(mat, c0: int, c1: int, cpu: bool = False, threads: int = 16, device_id: int = 0,
+                         walk_log2: int = 0, return_stats: bool = False):
+    """The part of perman_complex's sum from wave-chunks [c0, c1) of its plan,
+    folded pairwise over c - c0 and not scaled by 4(n&1)-2: aligned
+    power-of-two ranges folded pairwise in order, then scaled, reproduce
+    perman_complex's bits.  One device, or (cpu=True) host threads."""
+    a, n = _cmat(mat)
+    lib = _lib.load()
+    o = _opts(device_id=device_id, threads=threads, walk_log2=walk_log2)
+    re, im, st = C.c_double(0.0), C.c_double(0.0), SupStats()
+    _lib.check(lib.sup_perman_complex_range(a.ctypes.data, n, int(c0), int(c1), C.byref(o), int(bool(cpu)),
+                                            C.byref(re), C.byref(im), C.byref(st)), "perman_complex_range")
+    v = complex(re.value, im.value)
+    return (v, st.as_dict()) if return_stats else v
 
 
 def partial(mat, start: int, end: int, kernel: str = "dense", gpu_num: int = 1, device_id: int = 0,
@@ -512,6 +556,22 @@ def read_mtx(path: str, binary: bool = False) -> tuple[np.ndarray, str, int]:
     finally:
         lib.sup_free(p)
     return m, _TYPE_NAME[t.value], nnz.value
+
+
+def read_mtx_complex(path: str) -> tuple[np.ndarray, int]:
+    """MatrixMarket coordinate file whose field is `complex` -> (complex128
+    matrix, nz lines): general, symmetric (same value mirrored) or hermitian
+    (conjugate mirrored, real diagonal); n <= 64."""
+    lib = _lib.load()
+    p, n, nnz = C.c_void_p(), C.c_int(), C.c_int()
+    _lib.check(lib.sup_read_mtx_complex(os.fsencode(path), C.byref(p), C.byref(n), C.byref(nnz)),
+               f"read_mtx_complex({path})")
+    try:
+        buf = (C.c_char * (n.value * n.value * 16)).from_address(p.value)
+        m = np.frombuffer(buf, dtype=np.complex128).reshape(n.value, n.value).copy()
+    finally:
+        lib.sup_free(p)
+    return m, nnz.value
 
 
 # main.cu:77-103 / 156-183 (GPU) and 193-243 (CPU) approximation dispatch:

@@ -323,6 +323,63 @@ int sup_perman_quad(const void* mat, sup_dtype t, int n, const sup_opts* o_in, i
   return SUP_OK;
 }
 
+// sup_stats of a complex call over `steps` Gray steps (est_ops_per_step: 6n, the header's figure).
+static void fill_cplx_stats(sup_stats* st, const CplxInfo& ci, int n, uint64_t steps, double wall_ms) {
+  if (!st) return;
+  std::memset(st, 0, sizeof(*st));
+  st->kernel_ms = ci.kernel_ms;
+  st->wall_ms = wall_ms;
+  st->gray_steps = steps;
+  st->visited_steps = steps;
+  st->devices_used = ci.devices;
+  st->lane_bits = ci.lay.L;
+  st->walk_bits = ci.lay.m;
+  st->grid = ci.grid;
+  st->walk_kind = (int)kWalkDense;
+  st->leaves = 1;
+  st->est_ops_per_step = 6.0 * n;
+}
+
+int sup_perman_complex(const double* mat, int n, const sup_opts* o_in, int on_cpu, double* out_re, double* out_im,
+                       sup_stats* st) {
+  auto t0 = std::chrono::steady_clock::now();
+  if (!mat || !out_re || !out_im) {
+    set_error("sup_perman_complex: null matrix or output pointer");
+    return SUP_EINVAL;
+  }
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  double re = 0.0, im = 0.0;
+  CplxInfo ci;
+  if (int rc = cplx_perman(mat, n, o, on_cpu != 0, &re, &im, &ci)) return rc;
+  *out_re = re;
+  *out_im = im;
+  const double wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  fill_cplx_stats(st, ci, n, 1ull << (n - 1), wall);
+  return SUP_OK;
+}
+
+int sup_perman_complex_range(const double* mat, int n, uint64_t c0, uint64_t c1, const sup_opts* o_in, int on_cpu,
+                             double* out_re, double* out_im, sup_stats* st) {
+  auto t0 = std::chrono::steady_clock::now();
+  if (!mat || !out_re || !out_im) {
+    set_error("sup_perman_complex_range: null matrix or output pointer");
+    return SUP_EINVAL;
+  }
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  double re = 0.0, im = 0.0;
+  CplxInfo ci;
+  if (int rc = cplx_perman_range(mat, n, c0, c1, o, on_cpu != 0, &re, &im, &ci)) return rc;
+  *out_re = re;
+  *out_im = im;
+  const double wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  fill_cplx_stats(st, ci, n, (c1 - c0) << (ci.lay.L + ci.lay.m), wall);
+  return SUP_OK;
+}
+
 int sup_perman_reduced_exact(const void* mat, sup_dtype t, int n, const sup_opts* o_in, int on_cpu,
                              const sup_reduce_opts* r_in, char* out, size_t out_len, sup_stats* st) {
   auto t0 = std::chrono::steady_clock::now();

@@ -84,7 +84,7 @@ struct DeviceCtx {
   unsigned* d_visited = nullptr;
   double* d_wave = nullptr;   // exact path: per-wave residues
   size_t wave_cap = 0;
-  double* d_x0dd = nullptr;   // double-double walk: start vector (hi, lo)
+  double* d_x0dd = nullptr;   // two-block start vectors: double-double walk (hi, lo), complex walk (re, im)
   size_t x0dd_cap = 0;
   size_t visited_cap = 0;
   // queue heads and the fused fold's visited accumulator: head 0 at [0], head 1
@@ -922,6 +922,44 @@ int run_range_dd(int dev, const Plan& P, const std::vector<double>& x0dd, uint64
   SUP_HIP(blocked ? launch_dd_blocked(P.n, p, (int)grid, s) : launch_dd(P.n, p, (int)grid, s));
   SUP_HIP(hipEventRecord(c->ev1, s));
   SUP_HIP(hipMemcpyAsync(parts, c->d_chunk, 2 * count * sizeof(double), hipMemcpyDeviceToHost, s));
+  return timed_sync(c, kernel_ms);
+}
+
+// Complex fp64 walk (walk_cplx.hip) over wave-chunks [c0, c1) of a dense
+// identity plan whose column table holds the Re plane, then the Im plane.
+// The start vector (re block, im block) shares the double-double walk's
+// two-block buffer.
+int run_range_cplx(int dev, const Plan& P, const std::vector<double>& x0c, uint64_t c0, uint64_t c1, double* parts,
+                   double* kernel_ms, int* grid_out) {
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (grid_out) *grid_out = 0;
+  if (c1 <= c0) return SUP_OK;
+  const size_t plane = (size_t)2 * std::max(P.n - 1, 1) * P.NP;
+  if (P.kind != kWalkDense || c1 > P.lay.chunks() || x0c.size() != 2 * (size_t)P.NP || P.cols.size() != 2 * plane) {
+    set_error("run_range_cplx: bad request");
+    return SUP_EINVAL;
+  }
+  CtxGuard guard;
+  int rc = guard.open(dev, "device buffers");
+  if (rc) return rc;
+  DeviceCtx* c = guard.c;
+  int occ = 0;
+  SUP_HIP(cplx_occupancy(P.n, &occ));
+  const uint64_t count = c1 - c0;
+  const uint64_t grid = capped_grid(c, occ, count);
+  if ((rc = ensure(c->d_cols, c->cols_cap, P.cols.size()))) return rc;
+  if ((rc = ensure(c->d_x0dd, c->x0dd_cap, x0c.size()))) return rc;
+  if ((rc = ensure(c->d_chunk, c->chunk_cap, (size_t)(2 * count)))) return rc;
+  hipStream_t s = c->stream;
+  if ((rc = upload_walk_tables(c, P, c->d_x0dd, x0c))) return rc;
+  WalkParams p = walk_params(P, c->d_cols, c->d_x0dd, c0, count, c->d_counter, 1, false);
+  p.chunk_out = c->d_chunk;
+  SUP_HIP(hipEventRecord(c->ev0, s));
+  SUP_ON_DEVICE(c->dev, "complex walk launch");
+  SUP_HIP(launch_cplx(P.n, p, (int)grid, s));
+  SUP_HIP(hipEventRecord(c->ev1, s));
+  SUP_HIP(hipMemcpyAsync(parts, c->d_chunk, 2 * count * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (grid_out) *grid_out = (int)grid;
   return timed_sync(c, kernel_ms);
 }
 

@@ -446,4 +446,27 @@ int decompose_dd_batched(const double* A, int n, const sup_reduce_opts& r, int w
 int quad_perman(const double* A, int n, const sup_opts& o, bool on_cpu, double* hi, double* lo, double* kernel_ms,
                 int* devices_used);
 
+// ---- complex fp64 walk (cplx.cpp, walk_cplx.hip) ----
+// Wave-chunk partials (re, im) of chunks [c0, c1) of the complex plan P — a
+// dense identity plan whose P.cols holds the Re plane of the signed column
+// table, then the Im plane (each 2 max(n-1, 1) x NP) — with the start vector
+// x0c (2 NP: re block, im block) into parts[2 (c - c0) + {0, 1}]: on device
+// `dev` (*grid = blocks launched), or on host threads (bit-identical).
+int run_range_cplx(int dev, const Plan& P, const std::vector<double>& x0c, uint64_t c0, uint64_t c1, double* parts,
+                   double* kernel_ms, int* grid = nullptr);
+void cpu_cplx_range(const Plan& P, const std::vector<double>& x0c, uint64_t c0, uint64_t c1, int threads,
+                    double* parts);
+// What a complex call reports beside its value (sup_stats).
+struct CplxInfo {
+  double kernel_ms = 0.0;
+  int devices = 0, grid = 0;
+  Layout lay{};
+};
+// Permanent of the complex n x n matrix A (row-major, interleaved re, im).
+int cplx_perman(const double* A, int n, const sup_opts& o, bool on_cpu, double* re, double* im, CplxInfo* info);
+// The part of its sum from wave-chunks [c0, c1), folded pairwise over c - c0,
+// not scaled by 4(n&1) - 2; one device (o.device_id) or host threads.
+int cplx_perman_range(const double* A, int n, uint64_t c0, uint64_t c1, const sup_opts& o, bool on_cpu, double* re,
+                      double* im, CplxInfo* info);
+
 }  // namespace sup

@@ -70,6 +70,14 @@ SUP_DECL_DDB(17)
 SUP_DECL_DDB(33)
 SUP_DECL_DDB(49)
 #undef SUP_DECL_DDB
+#define SUP_DECL_CPLX(LO)                                                              \
+  hipError_t launch_cplx_##LO(int n, const WalkParams& p, int grid, hipStream_t s);   \
+  hipError_t occupancy_cplx_##LO(int n, int* blocks_per_cu);
+SUP_DECL_CPLX(1)
+SUP_DECL_CPLX(17)
+SUP_DECL_CPLX(33)
+SUP_DECL_CPLX(49)
+#undef SUP_DECL_CPLX
 #define SUP_DECL_LDS(LO)                                                                   \
   hipError_t launch_lds_##LO(int n, const WalkParams& p, int grid, hipStream_t s);        \
   hipError_t occupancy_lds_##LO(int n, int m, int* blocks_per_cu);
@@ -109,6 +117,12 @@ hipError_t dd_occupancy(int n, int* blocks_per_cu);
 // Its prefix-blocked form (walk_dd_blocked, a kWalkSparse plan: p.nb_lo / nb_hi).
 hipError_t launch_dd_blocked(int n, const WalkParams& p, int grid, hipStream_t s);
 hipError_t dd_blocked_occupancy(int n, int* blocks_per_cu);
+
+// Complex fp64 dense walk (walk_cplx.hip): p.cols = the Re plane, then the Im
+// plane of the signed column table; p.x0 = 2 NP doubles (re, im);
+// p.chunk_out = 2 doubles (re, im) per wave-chunk.
+hipError_t launch_cplx(int n, const WalkParams& p, int grid, hipStream_t s);
+hipError_t cplx_occupancy(int n, int* blocks_per_cu);
 
 // Fixed-order pairwise reduction of `count` doubles into *out (64-way passes,
 // zero padded; mirrored by oracle/oracle.c orc_pairwise_reduce).  `scratch`

@@ -19,6 +19,11 @@
 // dense walk in double-double (sup_perman_quad), -d devices with -p5/-p6,
 // -t host threads with -c; with -o / -u every leaf and the combine in
 // double-double (sup_perman_reduced_quad); prints hi and the hi + lo pair.
+// --complex (no short letter): the permanent of a MatrixMarket `complex`
+// file (sup_read_mtx_complex + sup_perman_complex): the dense walk over
+// complex fp64 values on -d devices from -l with -g, on -t host threads with
+// -c; prints "Permanent: <re> <im>".  It does not combine with -s, -o, -u,
+// -E, -q, -a, -b, -i or -r.
 #include <getopt.h>
 
 #include <chrono>
@@ -37,7 +42,7 @@ namespace {
 struct Cli {
   bool generic = true, dense = true, approximation = false, gpu = false, cpu = false, grid_graph = false;
   bool rccl = false, verbose = false, compression = false, exact = false, quad = false;
-  bool half_calc = false, half_store = false;
+  bool half_calc = false, half_store = false, complex = false, preprocessing_given = false, gpu_num_given = false;
   int gpu_num = 2, threads = 16, perman_algo = 1, preprocessing = 0, device = 0, reps = 1;
   double scaling = -1.0;
   long number_of_times = 100000;  // main.cu:338-344 defaults
@@ -124,6 +129,46 @@ int run_approx(const Cli& c) {
   return 0;
 }
 
+// --complex: the complex fp64 walk (sup_perman_complex) of a MatrixMarket
+// `complex` file; same line shape as -q.
+int run_complex(const Cli& c) {
+  const struct {
+    bool on;
+    const char* opt;
+  } refused[] = {{!c.dense, "-s"},       {c.compression, "-o"},  {c.scaling > 0.0, "-u"},
+                 {c.exact, "-E"},        {c.quad, "-q"},         {c.approximation, "-a"},
+                 {!c.generic, "-b"},     {c.grid_graph, "-i"},   {c.preprocessing_given, "-r"}};
+  for (const auto& r : refused)
+    if (r.on) {
+      std::fprintf(stderr, "perman: --complex does not combine with %s\n", r.opt);
+      return 1;
+    }
+  double* mat = nullptr;
+  int n = 0, nnz = 0;
+  if (sup_read_mtx_complex(c.filename.c_str(), &mat, &n, &nnz) != SUP_OK) return fail("reading complex matrix");
+  sup_opts o;
+  sup_opts_init(&o);
+  o.gpu_num = (c.gpu && c.gpu_num_given) ? c.gpu_num : 1;  // one device unless -d asks for more
+  o.device_id = c.device;
+  o.threads = c.threads;
+  double re = 0.0, im = 0.0;
+  sup_stats st;
+  int rc = SUP_OK;
+  const auto t0 = std::chrono::steady_clock::now();
+  for (int rep = 0; rep < c.reps && rc == SUP_OK; ++rep)
+    rc = sup_perman_complex(mat, n, &o, c.gpu ? 0 : 1, &re, &im, &st);
+  const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / (double)c.reps;
+  sup_free(mat);
+  if (rc != SUP_OK) return fail("complex permanent");
+  std::cout << "Result: " << (c.gpu ? "gpu_perman64_complex" : "cpu_perman64_complex") << " " << re << " " << im
+            << " in " << sec << std::endl;
+  std::printf("Permanent: %.17e %.17e\n", re, im);
+  if (c.verbose)
+    std::printf("Stats: devices %d kernel_ms %.3f wall_ms %.3f lanes %d walk %d grid %d\n", st.devices_used,
+                st.kernel_ms, st.wall_ms, st.lane_bits, st.walk_bits, st.grid);
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -144,6 +189,7 @@ int main(int argc, char** argv) {
                                         {"exact", 0, NULL, 'E'},         {"quad", 0, NULL, 'q'},
                                         {"halfCalc", 0, NULL, 'h'},      {"halfStore", 0, NULL, 'w'},
                                         {"gridMultip", 1, NULL, 'e'},    {"checkpoint", 1, NULL, 'C'},
+                                        {"complex", 0, NULL, 1000},
                                         {NULL, 0, NULL, 0}};
   int opt;
   auto need_arg = [&](char o) -> bool {
@@ -157,12 +203,12 @@ int main(int argc, char** argv) {
     switch (opt) {
       case 'b': c.generic = false; break;
       case 's': c.dense = false; break;
-      case 'r': if (!need_arg('t')) return 1; c.preprocessing = std::atoi(optarg); break;
+      case 'r': if (!need_arg('t')) return 1; c.preprocessing = std::atoi(optarg); c.preprocessing_given = true; break;
       case 't': if (!need_arg('t')) return 1; c.threads = std::atoi(optarg); break;
       case 'f': if (!need_arg('f')) return 1; c.filename = optarg; break;
       case 'a': c.approximation = true; break;
       case 'g': c.gpu = true; break;
-      case 'd': if (!need_arg('d')) return 1; c.gpu_num = std::atoi(optarg); break;
+      case 'd': if (!need_arg('d')) return 1; c.gpu_num = std::atoi(optarg); c.gpu_num_given = true; break;
       case 'c': c.cpu = true; break;
       case 'p': if (!need_arg('p')) return 1; c.perman_algo = std::atoi(optarg); break;
       case 'x': if (!need_arg('x')) return 1; c.number_of_times = std::atol(optarg); break;
@@ -179,6 +225,7 @@ int main(int argc, char** argv) {
       case 'R': c.rccl = true; break;
       case 'E': c.exact = true; break;
       case 'q': c.quad = true; break;
+      case 1000: c.complex = true; break;
       case 'v': c.verbose = true; break;
       // v2 flags (revised_perman/main.cpp:1431-1460): -w stores the matrix in
       // single precision (the permanent of the float-rounded entries); -h asks
@@ -206,6 +253,7 @@ int main(int argc, char** argv) {
   }
   for (int i = optind; i < argc; ++i) std::printf("Non-option argument %s\n", argv[i]);
   if (!c.cpu && !c.gpu) c.gpu = true;  // main.cu:482-484
+  if (c.complex) return run_complex(c);
   if (c.grid_graph || c.approximation) return run_approx(c);
 
   void* mat = nullptr;

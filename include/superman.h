@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SUP_ABI_VERSION 11  /* 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
+#define SUP_ABI_VERSION 12  /* 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SUP_OK            0
@@ -301,6 +301,49 @@ int sup_perman_complex(const double* mat, int n, const sup_opts* o, int on_cpu,
 int sup_perman_complex_range(const double* mat, int n, uint64_t c0, uint64_t c1,
                              const sup_opts* o, int on_cpu,
                              double* out_re, double* out_im, sup_stats* st);
+
+/* Many complex permanents in one call (ABI 12): boson-sampling simulators
+ * evaluate 10^4..10^7 permanents of n x n submatrices (n ~ 8..28) of one
+ * unitary per run, and one matrix of order n < 26 leaves most of an MI355X
+ * idle (one wave at n <= 13, 128 waves at n = 20).
+ * count permanents of n x n complex matrices: mats = count * 2 n^2 doubles
+ * (matrix k at mats + k*2*n*n, row-major interleaved re, im); out = 2*count
+ * doubles (re, im per matrix).
+ * Result k is bit-identical to sup_perman_complex of matrix k alone with the
+ * same o->walk_log2 — on the GPU, on any device count, on host threads and for
+ * any slab size: every matrix keeps its layout, chunk enumeration, operation
+ * order and the pairwise tree over its own chunk partials.
+ * n <= 32 on the device: slabs of matrices, each slab three launches (tables
+ * and start vectors written on the device, the batched walk walk_cplxb.hip
+ * over the wave-chunks of all its matrices in one queue, the per-matrix fold)
+ * and one download.  A slab holds as many matrices as keep its tables and
+ * partials under 256 MiB; the environment variable
+ * SUP_CPLX_BATCH_SLAB=<matrices> overrides that (tests).  n in 33..64: the
+ * matrices one after another through sup_perman_complex's walk.
+ * o->gpu_num devices from o->device_id take contiguous ranges of matrices
+ * (fewer matrices than devices: fewer devices); on_cpu = 1 runs the host twin
+ * on o->threads threads.  count == 0: SUP_OK, nothing written.  A null
+ * pointer, n outside [1, 64] or o->walk_log2 outside [0, 31]: SUP_EINVAL.
+ * Non-finite input propagates into its own result only.  No device with
+ * on_cpu = 0: SUP_ENODEV (no silent CPU fallback).
+ * st: kernel_ms (max over devices of the summed prepare, walk and fold kernel
+ * time), wall_ms, leaves = count, gray_steps = count 2^(n-1), devices_used,
+ * lane_bits, walk_bits, grid (last launch on the first device),
+ * est_ops_per_step = 6n. */
+int sup_perman_complex_batch(const double* mats, int n, uint64_t count, const sup_opts* o,
+                             int on_cpu, double* out, sup_stats* st);
+/* count permanents of n x n submatrices of one R x C complex matrix U
+ * (row-major interleaved): matrix k has entry (j, c) =
+ * U[rows[k*n + j]][cols[k*n + c]]; indices may repeat (photon collisions).
+ * On the device U goes up once and the gather happens where the tables are
+ * written: no submatrix is materialised.  Everything else as
+ * sup_perman_complex_batch (result k = sup_perman_complex of the gathered
+ * matrix, bit for bit).  R or C < 1, or an index outside [0, R) / [0, C):
+ * SUP_EINVAL — the message names k, the position and the value — before any
+ * device work. */
+int sup_perman_complex_submatrices(const double* U, int R, int C, const int32_t* rows,
+                                   const int32_t* cols, int n, uint64_t count, const sup_opts* o,
+                                   int on_cpu, double* out, sup_stats* st);
 
 /* Nijenhuis-Wilf prologue (gpu_exact_dense.cu:642-652): x0[j] = a[j][n-1] - rowsum_j/2,
  * p0 = prod x0.  Host-only helper, exported for the test harness. */

@@ -20,7 +20,7 @@ from ._lib import (KERNEL_DENSE, KERNEL_SKIPPER, KERNEL_SPARYSER, LEAF_FN, SCHED
                    SCHED_STATIC, SupApproxResult, SupError, SupOpts, SupReduceOpts, SupStats)
 
 __all__ = [
-    "perman", "perman_cpu", "perman_complex", "perman_complex_range", "read_mtx_complex", "partial", "perman_shard", "plan_info", "plan_key", "prepare", "read_matrix", "read_mtx", "sort_order",
+    "perman", "perman_cpu", "perman_complex", "perman_complex_range", "perman_complex_batch", "perman_complex_submatrices", "read_mtx_complex", "partial", "perman_shard", "plan_info", "plan_key", "prepare", "read_matrix", "read_mtx", "sort_order",
     "skip_order", "compress", "decompose", "perman_reduced", "approx", "grid_graph", "ALGOS_APPROX",
     "nw_start", "device_count", "rccl_devices", "layout", "ShardCall", "SupError", "ALGOS_DENSE", "ALGOS_SPARSE",
     "gpu_perman64_xshared_coalescing_mshared",
@@ -240,6 +240,68 @@ def perman_complex_range(mat, c0: int, c1: int, cpu: bool = False, threads: int 
     _lib.check(lib.sup_perman_complex_range(a.ctypes.data, n, int(c0), int(c1), C.byref(o), int(bool(cpu)),
                                             C.byref(re), C.byref(im), C.byref(st)), "perman_complex_range")
     v = complex(re.value, im.value)
+    return (v, st.as_dict()) if return_stats else v
+
+
+def _batch_result(out: np.ndarray, count: int) -> np.ndarray:
+    return out[: 2 * count].view(np.complex128).copy()
+
+
+def perman_complex_batch(mats, gpu_num: int = 1, device_id: int = 0, cpu: bool = False, threads: int = 16,
+                         walk_log2: int = 0, return_stats: bool = False):
+    """The permanents of ``count`` complex n x n matrices, ``mats`` of shape
+    [count, n, n], in one call (sup_perman_complex_batch): np.ndarray
+    complex128 of shape [count].  Result k is bit-identical to
+    ``perman_complex(mats[k])`` with the same ``walk_log2`` — on the GPU (the
+    batched walk walk_cplxb.hip for n <= 32), on any device count and
+    (cpu=True) on host threads."""
+    a = np.ascontiguousarray(np.asarray(mats, dtype=np.complex128))
+    if a.ndim != 3 or a.shape[1] != a.shape[2]:
+        raise ValueError(f"expected an array of shape [count, n, n], got shape {a.shape}")
+    count, n = a.shape[0], a.shape[1]
+    if not 1 <= n <= 64:
+        raise ValueError(f"n = {n} outside [1, 64] (64-bit Gray index)")
+    lib = _lib.load()
+    o = _opts(gpu_num=gpu_num, device_id=device_id, threads=threads, walk_log2=walk_log2)
+    out, st = np.zeros(2 * max(count, 1)), SupStats()
+    src = a if count else np.zeros(2)  # a valid pointer for an empty batch
+    _lib.check(lib.sup_perman_complex_batch(src.ctypes.data, n, count, C.byref(o), int(bool(cpu)), out.ctypes.data,
+                                            C.byref(st)), "perman_complex_batch")
+    v = _batch_result(out, count)
+    return (v, st.as_dict()) if return_stats else v
+
+
+def perman_complex_submatrices(U, rows, cols, gpu_num: int = 1, device_id: int = 0, cpu: bool = False,
+                               threads: int = 16, walk_log2: int = 0, return_stats: bool = False):
+    """The permanents of ``count`` n x n submatrices of one complex matrix U:
+    ``rows`` and ``cols`` are integer arrays of shape [count, n], matrix k is
+    ``U[np.ix_(rows[k], cols[k])]`` (indices may repeat), gathered where the
+    walk's tables are written — on the device U is uploaded once
+    (sup_perman_complex_submatrices).  np.ndarray complex128 of shape [count],
+    bit-identical to ``perman_complex_batch`` of the gathered matrices."""
+    u = np.ascontiguousarray(np.asarray(U, dtype=np.complex128))
+    if u.ndim != 2 or u.shape[0] < 1 or u.shape[1] < 1:
+        raise ValueError(f"expected a non-empty 2-d matrix U, got shape {u.shape}")
+    r, c = np.asarray(rows), np.asarray(cols)
+    if r.ndim != 2 or r.shape != c.shape:
+        raise ValueError(f"rows and cols must both have shape [count, n], got {r.shape} and {c.shape}")
+    for name, ix in (("rows", r), ("cols", c)):
+        if ix.size and not np.issubdtype(ix.dtype, np.integer):
+            raise ValueError(f"{name} must be an integer array, got dtype {ix.dtype}")
+        if ix.size and (ix.min() < -2**31 or ix.max() >= 2**31):
+            raise ValueError(f"{name} holds an index outside the 32-bit range")
+    count, n = r.shape
+    if not 1 <= n <= 64:
+        raise ValueError(f"n = {n} outside [1, 64] (64-bit Gray index)")
+    r32 = np.ascontiguousarray(r, dtype=np.int32) if count else np.zeros(1, np.int32)
+    c32 = np.ascontiguousarray(c, dtype=np.int32) if count else np.zeros(1, np.int32)
+    lib = _lib.load()
+    o = _opts(gpu_num=gpu_num, device_id=device_id, threads=threads, walk_log2=walk_log2)
+    out, st = np.zeros(2 * max(count, 1)), SupStats()
+    _lib.check(lib.sup_perman_complex_submatrices(u.ctypes.data, u.shape[0], u.shape[1], r32.ctypes.data,
+                                                  c32.ctypes.data, n, count, C.byref(o), int(bool(cpu)),
+                                                  out.ctypes.data, C.byref(st)), "perman_complex_submatrices")
+    v = _batch_result(out, count)
     return (v, st.as_dict()) if return_stats else v
 
 

@@ -380,6 +380,43 @@ int sup_perman_complex_range(const double* mat, int n, uint64_t c0, uint64_t c1,
   return SUP_OK;
 }
 
+// Both batched complex entries: `in` names the matrices (raw or U + index lists).
+static int complex_batch(const CplxBatchIn& in, int n, uint64_t count, const sup_opts* o_in, int on_cpu, double* out,
+                         sup_stats* st) {
+  auto t0 = std::chrono::steady_clock::now();
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  CplxInfo ci;
+  if (int rc = cplx_perman_batch(in, n, count, o, on_cpu != 0, out, &ci)) return rc;
+  const double wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  fill_cplx_stats(st, ci, n, count << (n - 1), wall);
+  if (st) st->leaves = (int)std::min<uint64_t>(count, 0x7fffffffu);
+  return SUP_OK;
+}
+
+int sup_perman_complex_batch(const double* mats, int n, uint64_t count, const sup_opts* o, int on_cpu, double* out,
+                             sup_stats* st) {
+  if (!mats || !out) {
+    set_error("sup_perman_complex_batch: null matrix or output pointer");
+    return SUP_EINVAL;
+  }
+  CplxBatchIn in;
+  in.mats = mats;
+  return complex_batch(in, n, count, o, on_cpu, out, st);
+}
+
+int sup_perman_complex_submatrices(const double* U, int R, int C, const int32_t* rows, const int32_t* cols, int n,
+                                   uint64_t count, const sup_opts* o, int on_cpu, double* out, sup_stats* st) {
+  if (!U || !rows || !cols || !out) {
+    set_error("sup_perman_complex_submatrices: null matrix, index list or output pointer");
+    return SUP_EINVAL;
+  }
+  CplxBatchIn in;
+  in.U = U, in.R = R, in.C = C, in.rows = rows, in.cols = cols;
+  return complex_batch(in, n, count, o, on_cpu, out, st);
+}
+
 int sup_perman_reduced_exact(const void* mat, sup_dtype t, int n, const sup_opts* o_in, int on_cpu,
                              const sup_reduce_opts* r_in, char* out, size_t out_len, sup_stats* st) {
   auto t0 = std::chrono::steady_clock::now();

@@ -1,5 +1,7 @@
 // cplx.cpp — the permanent of a complex fp64 matrix: sup_perman_complex and
-// sup_perman_complex_range.  The reference has no counterpart ("SUPerman does
+// sup_perman_complex_range, and many of them in one call:
+// sup_perman_complex_batch and sup_perman_complex_submatrices
+// (cplx_perman_batch at the end of this file).  The reference has no counterpart ("SUPerman does
 // not support complex type", revised_perman/main.cpp:1557).
 //
 // Plan: the dense identity plan of Re A (default layout, or o.walk_log2 walk
@@ -116,6 +118,19 @@ cx cx_pairwise(const double* parts, uint64_t count) {
   return v[0];
 }
 
+// The layout of a complex walk of order n: the default layout, or o.walk_log2
+// walk bits (n in [1, 64], o.walk_log2 in [0, 31]).
+Layout cplx_layout(int n, const sup_opts& o) {
+  Layout lay = default_layout(n);
+  if (o.walk_log2 > 0) {
+    const int rest = n - 1 - lay.L;
+    lay.m = std::min(o.walk_log2, rest);
+    lay.h = rest - lay.m;
+    lay.fixed = true;
+  }
+  return lay;
+}
+
 // The plan (column planes Re, Im in P.cols) and start vector of A, n x n
 // row-major interleaved (re, im).
 int cplx_plan(const double* A, int n, const sup_opts& o, Plan& P, std::vector<double>& x0c) {
@@ -131,13 +146,7 @@ int cplx_plan(const double* A, int n, const sup_opts& o, Plan& P, std::vector<do
     set_error("walk_log2 = " + std::to_string(o.walk_log2) + " outside [0, 31] (0 = default layout)");
     return SUP_EINVAL;
   }
-  Layout lay = default_layout(n);
-  if (o.walk_log2 > 0) {
-    const int rest = n - 1 - lay.L;
-    lay.m = std::min(o.walk_log2, rest);
-    lay.h = rest - lay.m;
-    lay.fixed = true;
-  }
+  const Layout lay = cplx_layout(n, o);
   const size_t nn = (size_t)n * n;
   std::vector<double> Ar(nn), Ai(nn);
   for (size_t i = 0; i < nn; ++i) Ar[i] = A[2 * i], Ai[i] = A[2 * i + 1];
@@ -268,6 +277,153 @@ int cplx_perman(const double* A, int n, const sup_opts& o, bool on_cpu, double* 
   const double f = 4.0 * (n & 1) - 2.0;
   *re = f * total.re;
   *im = f * total.im;
+  if (info) *info = ci;
+  return SUP_OK;
+}
+
+// ---- batched permanents: sup_perman_complex_batch, sup_perman_complex_submatrices ----
+// Result k is cplx_perman's of matrix k alone (same walk bits), bit for bit:
+// every matrix keeps its layout, chunk enumeration, cx.hpp operation order and
+// the pairwise tree over its own chunk partials.  n <= 32 on the device: the
+// batched walk (run_cplx_batch), o.gpu_num devices taking contiguous ranges of
+// matrices, one host thread each.  n > 32 (one matrix already fills the chip):
+// the matrices one after another through cplx_perman.  on_cpu: cplx_plan,
+// cpu_cplx_range and cx_pairwise per matrix, o.threads host threads spread
+// over the matrices, or over one matrix's chunks when there are fewer
+// matrices than threads.
+int cplx_perman_batch(const CplxBatchIn& in, int n, uint64_t count, const sup_opts& o, bool on_cpu, double* out,
+                      CplxInfo* info) {
+  const bool sub = in.U != nullptr;
+  const char* who = sub ? "sup_perman_complex_submatrices" : "sup_perman_complex_batch";
+  if (!out || (!sub && !in.mats) || (sub && (!in.rows || !in.cols))) {
+    set_error(std::string(who) + ": null pointer");
+    return SUP_EINVAL;
+  }
+  if (n < 1 || n > SUP_MAX_N) {
+    set_error("n = " + std::to_string(n) + " outside [1, 64] (64-bit Gray index)");
+    return SUP_EINVAL;
+  }
+  if (o.walk_log2 < 0 || o.walk_log2 > 31) {
+    set_error("walk_log2 = " + std::to_string(o.walk_log2) + " outside [0, 31] (0 = default layout)");
+    return SUP_EINVAL;
+  }
+  if (sub && (in.R < 1 || in.C < 1)) {
+    set_error(std::string(who) + ": U must have at least one row and one column (R = " + std::to_string(in.R) +
+              ", C = " + std::to_string(in.C) + ")");
+    return SUP_EINVAL;
+  }
+  if (sub)
+    for (uint64_t k = 0; k < count; ++k)
+      for (int j = 0; j < n; ++j) {
+        const int32_t r = in.rows[k * n + j], c = in.cols[k * n + j];
+        if (r < 0 || r >= in.R || c < 0 || c >= in.C) {
+          const bool row_bad = r < 0 || r >= in.R;
+          set_error(std::string(who) + ": " + (row_bad ? "rows" : "cols") + "[k = " + std::to_string(k) +
+                    "][position " + std::to_string(j) + "] = " + std::to_string(row_bad ? r : c) + " outside [0, " +
+                    std::to_string(row_bad ? in.R : in.C) + ")");
+          return SUP_EINVAL;
+        }
+      }
+  CplxInfo ci;
+  ci.lay = cplx_layout(n, o);
+  if (info) *info = ci;
+  if (count == 0) return SUP_OK;
+  const size_t nn = (size_t)n * n;
+  // matrix k, n x n interleaved: in place (raw form) or gathered into buf
+  auto matrix = [&](uint64_t k, std::vector<double>& buf) -> const double* {
+    if (!sub) return in.mats + k * 2 * nn;
+    buf.resize(2 * nn);
+    for (int j = 0; j < n; ++j) {
+      const double* urow = in.U + 2 * (size_t)in.rows[k * n + j] * in.C;
+      for (int c = 0; c < n; ++c) {
+        const double* v = urow + 2 * (size_t)in.cols[k * n + c];
+        buf[2 * ((size_t)j * n + c)] = v[0];
+        buf[2 * ((size_t)j * n + c) + 1] = v[1];
+      }
+    }
+    return buf.data();
+  };
+  if (on_cpu) {
+    const int T = std::max(o.threads, 1);
+    auto one = [&](uint64_t k, int threads, std::vector<double>& buf, std::vector<double>& parts) -> int {
+      try {
+        Plan P;
+        std::vector<double> x0c;
+        if (int rc = cplx_plan(matrix(k, buf), n, o, P, x0c)) return rc;
+        const uint64_t C = P.lay.chunks();
+        parts.assign(2 * (size_t)C, 0.0);
+        cpu_cplx_range(P, x0c, 0, C, threads, parts.data());
+        const cx total = cx_pairwise(parts.data(), C);
+        const double f = 4.0 * (n & 1) - 2.0;
+        out[2 * k] = f * total.re;
+        out[2 * k + 1] = f * total.im;
+        return SUP_OK;
+      } catch (const std::bad_alloc&) {
+        set_error("out of host memory for the wave-chunk partials of matrix " + std::to_string(k));
+        return SUP_ENOMEM;
+      }
+    };
+    if (count < (uint64_t)T) {  // few matrices: the threads share each matrix's chunks
+      std::vector<double> buf, parts;
+      for (uint64_t k = 0; k < count; ++k)
+        if (int rc = one(k, T, buf, parts)) return rc;
+    } else {
+      std::vector<int> wrc(T, SUP_OK);
+      std::vector<std::string> werr(T);  // g_err is thread_local: carry worker messages back
+      auto work = [&](int w) {
+        std::vector<double> buf, parts;
+        for (uint64_t k = (uint64_t)w; k < count && !wrc[w]; k += (uint64_t)T)
+          if ((wrc[w] = one(k, 1, buf, parts))) werr[w] = last_error();
+      };
+      std::vector<std::thread> th;
+      for (int w = 1; w < T; ++w) th.emplace_back(work, w);
+      work(0);
+      for (auto& t : th) t.join();
+      for (int w = 0; w < T; ++w)
+        if (wrc[w]) {
+          set_error(werr[w]);
+          return wrc[w];
+        }
+    }
+    if (info) *info = ci;
+    return SUP_OK;
+  }
+  int ndev = 0;
+  if (int rc = need_device(o, who, &ndev)) return rc;
+  if (n > 32) {
+    std::vector<double> buf;
+    for (uint64_t k = 0; k < count; ++k) {
+      CplxInfo one;
+      if (int rc = cplx_perman(matrix(k, buf), n, o, false, &out[2 * k], &out[2 * k + 1], &one)) return rc;
+      ci.kernel_ms += one.kernel_ms;
+      ci.grid = one.grid;
+      ci.devices = one.devices;
+    }
+    if (info) *info = ci;
+    return SUP_OK;
+  }
+  const int G =
+      (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::max(1, std::min(o.gpu_num, ndev - o.device_id)), count));
+  std::vector<int> drc(G, SUP_OK), dgrid(G, 0);
+  std::vector<double> dms(G, 0.0);
+  std::vector<std::string> derr(G);
+  auto work = [&](int g) {
+    const uint64_t a = count * (uint64_t)g / (uint64_t)G, b = count * (uint64_t)(g + 1) / (uint64_t)G;
+    drc[g] = run_cplx_batch(o.device_id + g, n, ci.lay, in, a, b, out + 2 * a, &dms[g], &dgrid[g]);
+    if (drc[g]) derr[g] = last_error();
+  };
+  std::vector<std::thread> th;
+  for (int g = 1; g < G; ++g) th.emplace_back(work, g);
+  work(0);
+  for (auto& t : th) t.join();
+  for (int g = 0; g < G; ++g)
+    if (drc[g]) {
+      set_error(derr[g]);
+      return drc[g];
+    }
+  ci.kernel_ms = *std::max_element(dms.begin(), dms.end());
+  ci.grid = dgrid[0];
+  ci.devices = G;
   if (info) *info = ci;
   return SUP_OK;
 }

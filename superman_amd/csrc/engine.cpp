@@ -109,6 +109,18 @@ struct DeviceCtx {
   size_t bres_cap = 0;
   double* h_bres = nullptr;  // pinned, kMaxBatchLeaves doubles
   int occ_batch[2][SUP_MAX_N + 1] = {};
+  // batched complex walk (run_cplx_batch): a slab's tables + start vectors,
+  // its raw matrices or index lists, the submatrix form's U, its results
+  double* d_cbtab = nullptr;
+  size_t cbtab_cap = 0;
+  double* d_cbmat = nullptr;
+  size_t cbmat_cap = 0;
+  int32_t* d_cbidx = nullptr;
+  size_t cbidx_cap = 0;
+  double* d_cbU = nullptr;
+  size_t cbU_cap = 0;
+  double* d_cbout = nullptr;
+  size_t cbout_cap = 0;
   uint64_t tables_uid = 0;  // Plan::uid whose cols / x0 / nblk / rowmask / jtab the device holds
   std::mutex mu;
   int occ[3][SUP_MAX_N + 1] = {};  // AOT kernels; segmented walk: jit_occupancy
@@ -961,6 +973,101 @@ int run_range_cplx(int dev, const Plan& P, const std::vector<double>& x0c, uint6
   SUP_HIP(hipMemcpyAsync(parts, c->d_chunk, 2 * count * sizeof(double), hipMemcpyDeviceToHost, s));
   if (grid_out) *grid_out = (int)grid;
   return timed_sync(c, kernel_ms);
+}
+
+// Batched complex walk (walk_cplxb.hip, cplx_batch.hip) of matrices [k0, k1)
+// of `in` (order n <= 32, layout lay) on device `dev`, in slabs of K matrices:
+// per slab one upload of its raw matrices (or its index lists; U goes up once
+// per call), then prepare, walk and fold on the context's stream with no host
+// work between them, and one download of 16 K bytes into out[2 (k - k0)].
+// K: as many matrices as keep a slab's tables, partials and input under
+// kCplxBatchCapBytes (at least one), or SUP_CPLX_BATCH_SLAB.
+static constexpr size_t kCplxBatchCapBytes = (size_t)256 << 20;
+int run_cplx_batch(int dev, int n, const Layout& lay, const CplxBatchIn& in, uint64_t k0, uint64_t k1, double* out,
+                   double* kernel_ms, int* grid_out) {
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (grid_out) *grid_out = 0;
+  if (k1 <= k0) return SUP_OK;
+  if (n < 1 || n > 32 || lay.L + lay.m + lay.h != n - 1 || lay.h > 24 || (!in.mats && !(in.U && in.rows && in.cols))) {
+    set_error("run_cplx_batch: bad request");
+    return SUP_EINVAL;
+  }
+  const bool sub = in.U != nullptr;
+  const size_t NP = (size_t)pad8(n), plane = (size_t)2 * std::max(n - 1, 1) * NP, nn = (size_t)n * n;
+  const size_t tab = 2 * plane, per_chunks = (size_t)1 << lay.h;
+  const size_t per_bytes = (tab + 2 * NP + 2 * per_chunks + 2 + (sub ? (size_t)n : 2 * nn)) * sizeof(double);
+  uint64_t K = std::max<uint64_t>(1, kCplxBatchCapBytes / per_bytes);
+  if (const char* e = std::getenv("SUP_CPLX_BATCH_SLAB")) {
+    const long long v = std::atoll(e);
+    if (v > 0) K = (uint64_t)v;
+  }
+  K = std::min({K, k1 - k0, (uint64_t)0x7fffffffu >> lay.h});  // 32-bit queue tickets
+  CtxGuard guard;
+  int rc = guard.open(dev, "device buffers");
+  if (rc) return rc;
+  DeviceCtx* c = guard.c;
+  int occ = 0;
+  SUP_HIP(cplx_batch_occupancy(n, &occ));
+  if ((rc = ensure(c->d_cbtab, c->cbtab_cap, (size_t)K * (tab + 2 * NP)))) return rc;
+  if ((rc = ensure(c->d_chunk, c->chunk_cap, (size_t)K * 2 * per_chunks))) return rc;
+  if ((rc = ensure(c->d_cbout, c->cbout_cap, (size_t)K * 2))) return rc;
+  if (sub) {
+    if ((rc = ensure(c->d_cbidx, c->cbidx_cap, (size_t)K * 2 * n))) return rc;
+    if ((rc = ensure(c->d_cbU, c->cbU_cap, (size_t)2 * in.R * in.C))) return rc;
+  } else if ((rc = ensure(c->d_cbmat, c->cbmat_cap, (size_t)K * 2 * nn))) {
+    return rc;
+  }
+  hipStream_t s = c->stream;
+  c->tables_uid = 0;  // the walk leaves head 0 nonzero
+  c->head_zero[0] = false;
+  if (sub)
+    SUP_HIP(hipMemcpyAsync(c->d_cbU, in.U, (size_t)2 * in.R * in.C * sizeof(double), hipMemcpyHostToDevice, s));
+  double* d_tabs = c->d_cbtab;
+  double* d_x0s = c->d_cbtab + (size_t)K * tab;
+  const uint64_t resident = (uint64_t)c->cus * (uint64_t)std::max(occ, 1);
+  double total_ms = 0.0;
+  for (uint64_t a = k0; a < k1; a += K) {
+    const uint64_t kk = std::min(K, k1 - a);
+    CplxBatchSrc src{};
+    if (sub) {
+      int32_t* d_rows = c->d_cbidx;
+      int32_t* d_cols = c->d_cbidx + (size_t)K * n;
+      SUP_HIP(hipMemcpyAsync(d_rows, in.rows + a * n, (size_t)kk * n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+      SUP_HIP(hipMemcpyAsync(d_cols, in.cols + a * n, (size_t)kk * n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+      src.U = c->d_cbU, src.rows = d_rows, src.cols = d_cols, src.C = in.C;
+    } else {
+      SUP_HIP(hipMemcpyAsync(c->d_cbmat, in.mats + a * 2 * nn, (size_t)kk * 2 * nn * sizeof(double),
+                             hipMemcpyHostToDevice, s));
+      src.mats = c->d_cbmat;
+    }
+    SUP_HIP(hipMemsetAsync(c->d_counter, 0, sizeof(unsigned), s));
+    const uint64_t chunks = kk << lay.h;
+    const LaunchGeom geo = walk_geometry(chunks, resident, kWavesPerBlock, false);
+    WalkParams p{};
+    p.cols = d_tabs;
+    p.x0 = d_x0s;
+    p.chunk_begin = 0;
+    p.chunk_count = chunks;
+    p.L = lay.L;
+    p.m = lay.m;
+    p.n = n;
+    p.counter = c->d_counter;
+    p.group = geo.group;
+    p.chunk_out = c->d_chunk;
+    SUP_HIP(hipEventRecord(c->ev0, s));
+    SUP_ON_DEVICE(c->dev, "batched complex walk launch");
+    SUP_HIP(launch_cplx_batch_prepare(src, n, kk, d_tabs, d_x0s, s));
+    SUP_HIP(launch_cplx_batch(n, p, lay.h, (int)geo.grid, s));
+    SUP_HIP(launch_cplx_batch_fold(c->d_chunk, n, lay.h, kk, c->d_cbout, s));
+    SUP_HIP(hipEventRecord(c->ev1, s));
+    SUP_HIP(hipMemcpyAsync(out + 2 * (a - k0), c->d_cbout, (size_t)kk * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+    double ms = 0.0;
+    if ((rc = timed_sync(c, &ms))) return rc;
+    total_ms += ms;
+    if (grid_out) *grid_out = (int)geo.grid;
+  }
+  if (kernel_ms) *kernel_ms = total_ms;
+  return SUP_OK;
 }
 
 }  // namespace sup

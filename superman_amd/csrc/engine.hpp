@@ -469,4 +469,27 @@ int cplx_perman(const double* A, int n, const sup_opts& o, bool on_cpu, double* 
 int cplx_perman_range(const double* A, int n, uint64_t c0, uint64_t c1, const sup_opts& o, bool on_cpu, double* re,
                       double* im, CplxInfo* info);
 
+// ---- batched complex permanents (cplx.cpp; walk_cplxb.hip, cplx_batch.hip) ----
+// `count` matrices of order n (host pointers): `mats`, count x 2 n^2 doubles,
+// or — U non-null — submatrices of the R x C matrix U (row-major interleaved):
+// matrix k has entry (j, c) = U[rows[k n + j]][cols[k n + c]].
+struct CplxBatchIn {
+  const double* mats = nullptr;
+  const double* U = nullptr;
+  int R = 0, C = 0;
+  const int32_t* rows = nullptr;
+  const int32_t* cols = nullptr;
+};
+// Permanents of matrices [k0, k1) of `in` (n <= 32) into out[2 (k - k0) +
+// {0, 1}] on device `dev`: each has the bits of cplx_perman on that matrix
+// alone with layout `lay`.  *kernel_ms: prepare + walk + fold kernel time
+// summed over the slabs; *grid: blocks of the last walk launch.
+int run_cplx_batch(int dev, int n, const Layout& lay, const CplxBatchIn& in, uint64_t k0, uint64_t k1, double* out,
+                   double* kernel_ms, int* grid = nullptr);
+// out[2k], out[2k + 1] = the permanent of matrix k of `in`, k < count
+// (sup_perman_complex_batch, sup_perman_complex_submatrices).  Arguments and
+// indices are checked before any work; count == 0 writes nothing.
+int cplx_perman_batch(const CplxBatchIn& in, int n, uint64_t count, const sup_opts& o, bool on_cpu, double* out,
+                      CplxInfo* info);
+
 }  // namespace sup

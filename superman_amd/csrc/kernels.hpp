@@ -78,7 +78,13 @@ SUP_DECL_CPLX(17)
 SUP_DECL_CPLX(33)
 SUP_DECL_CPLX(49)
 #undef SUP_DECL_CPLX
-#define SUP_DECL_LDS(LO)                                                                   \
+#define SUP_DECL_CPLXB(LO)                                                                        \
+  hipError_t launch_cplxb_##LO(int n, const WalkParams& p, int hbits, int grid, hipStream_t s); \
+  hipError_t occupancy_cplxb_##LO(int n, int* blocks_per_cu);
+SUP_DECL_CPLXB(1)
+SUP_DECL_CPLXB(17)
+#undef SUP_DECL_CPLXB
+#define SUP_DECL_LDS(LO)                                                                  \
   hipError_t launch_lds_##LO(int n, const WalkParams& p, int grid, hipStream_t s);        \
   hipError_t occupancy_lds_##LO(int n, int m, int* blocks_per_cu);
 SUP_DECL_LDS(1)
@@ -123,6 +129,31 @@ hipError_t dd_blocked_occupancy(int n, int* blocks_per_cu);
 // p.chunk_out = 2 doubles (re, im) per wave-chunk.
 hipError_t launch_cplx(int n, const WalkParams& p, int grid, hipStream_t s);
 hipError_t cplx_occupancy(int n, int* blocks_per_cu);
+
+// Batched complex walk (walk_cplxb.hip, n <= 32): the wave-chunks of
+// p.chunk_count >> hbits matrices in one queue; global chunk a is chunk
+// a & (2^hbits - 1) of matrix a >> hbits.  p.cols / p.x0 = the matrices'
+// tables / start vectors one after another (walk_cplx's layout each),
+// p.chunk_out = 2 doubles per global chunk.
+hipError_t launch_cplx_batch(int n, const WalkParams& p, int hbits, int grid, hipStream_t s);
+hipError_t cplx_batch_occupancy(int n, int* blocks_per_cu);
+// Where a slab's matrices come from (device pointers): `mats`, K matrices of
+// 2 n^2 doubles, or — U non-null — the R x C matrix U (row-major interleaved,
+// C its row length) and the slab's index lists (K x n each).
+struct CplxBatchSrc {
+  const double* mats;
+  const double* U;
+  const int32_t* rows;
+  const int32_t* cols;
+  int C;
+  int pad_;
+};
+// The tables and start vectors of K matrices of order n (cplx_batch.hip).
+hipError_t launch_cplx_batch_prepare(const CplxBatchSrc& src, int n, uint64_t K, double* tabs, double* x0s,
+                                     hipStream_t s);
+// out[2k], out[2k + 1] = (4(n&1) - 2) x the pairwise tree over matrix k's
+// 2^hbits (re, im) partials at parts + 2 (k << hbits).
+hipError_t launch_cplx_batch_fold(const double* parts, int n, int hbits, uint64_t K, double* out, hipStream_t s);
 
 // Fixed-order pairwise reduction of `count` doubles into *out (64-way passes,
 // zero padded; mirrored by oracle/oracle.c orc_pairwise_reduce).  `scratch`

@@ -1,0 +1,90 @@
+"""Compiler resource report and walk-loop census of the complex walk kernels,
+by cross-compiling for gfx950 (no GPU needed).
+
+For every N of the chosen kernel it prints one line in the columns of
+profiles/complex/walk_cplx_resources.log: hipcc's
+-Rpass-analysis=kernel-resource-usage figures, then a scan of the -S output:
+the walk loop (the innermost loop with the most fp64 VALU instructions: one odd
++ one even Gray step, 2(6N - 2) of them) with its scratch instructions, AGPR
+moves, v_mov and readlane / writelane, and the scratch instructions of the
+whole kernel.
+
+  python tools/probes/cplx_resources.py batch > profiles/complex_batch/walk_cplx_batch_resources.log
+  python tools/probes/cplx_resources.py single --ranges 1_16 17_32   # walk_cplx<N>, to diff against its log
+"""
+import argparse
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "superman_amd", "csrc")
+KERNELS = {"batch": ("walk_cplxb.hip", "walk_cplx_batch", ["1_16", "17_32"]),
+           "single": ("walk_cplx.hip", "walk_cplx", ["1_16", "17_32", "33_48", "49_64"])}
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
+
+ap = argparse.ArgumentParser()
+ap.add_argument("kernel", choices=sorted(KERNELS))
+ap.add_argument("--ranges", nargs="*", default=None)
+ap.add_argument("--hipcc", default=os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))
+args = ap.parse_args()
+src, kname, ranges = KERNELS[args.kernel]
+ranges = args.ranges or ranges
+
+
+def census(body):
+    """Loops of one function's assembly as (first line, last line) of backward branches."""
+    labels = {m.group(1): i for i, l in enumerate(body) if (m := re.match(r"^(\.LBB\d+_\d+):", l))}
+    loops = []
+    for i, l in enumerate(body):
+        m = re.match(r"^\s*s_c?branch\w*\s+(\.LBB\d+_\d+)", l)
+        if m and labels.get(m.group(1), i) < i:
+            loops.append((labels[m.group(1)], i))
+    inner = [a for a in loops if not any(b != a and a[0] <= b[0] and b[1] <= a[1] for b in loops)]
+    count = lambda lines, rx: sum(1 for l in lines if re.match(rx, l))  # noqa: E731
+    f64 = r"^\s*v_\w+_f64"
+    scratch = r"^\s*(scratch_|buffer_load|buffer_store)"
+    best = max(inner, key=lambda a: count(body[a[0]:a[1] + 1], f64), default=None)
+    lines = body[best[0]:best[1] + 1] if best else []
+    return (count(lines, f64), count(lines, scratch), count(lines, r"^\s*v_accvgpr"), count(lines, r"^\s*v_mov_b"),
+            count(lines, r"^\s*v_(readlane|writelane)"), count(body, scratch))
+
+
+rows = {}
+for r in ranges:
+    lo, hi = r.split("_")
+    with tempfile.TemporaryDirectory() as tmp:
+        asm = os.path.join(tmp, "k.s")
+        p = subprocess.run([args.hipcc, *FLAGS, f"-DSUP_N_LO={lo}", f"-DSUP_N_HI={hi}", "--cuda-device-only", "-S",
+                            "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, src), "-o", asm],
+                           capture_output=True, text=True, cwd=CSRC)
+        if p.returncode:
+            sys.exit(p.stderr[-4000:])
+        text = open(asm).read().splitlines()
+    res, cur = {}, None
+    for l in p.stderr.splitlines():
+        if m := re.search(r"remark: Function Name: (\S+)", l):
+            k = re.search(rf"{kname}ILi(\d+)E", m.group(1))
+            cur = int(k.group(1)) if k else None
+            if cur is not None:
+                res[cur] = {}
+        elif cur is not None and (m := re.search(r"remark:\s+([A-Za-z \[\]/]+?): (\S+)", l)):
+            res[cur][m.group(1).strip()] = m.group(2)
+    for n, d in res.items():
+        start = next(i for i, l in enumerate(text) if re.match(rf"^_ZN3sup\d+{kname}ILi{n}E\w*:", l))
+        end = next(i for i in range(start, len(text)) if text[i].startswith(".Lfunc_end"))
+        c = census(text[start:end])
+        rows[n] = (f"{n} {d['Occupancy [waves/SIMD]']} {d['VGPRs']} {d['AGPRs']} {d['TotalSGPRs']} {d['VGPRs Spill']} "
+                   f"{d['SGPRs Spill']} {d['ScratchSize [bytes/lane]']} | {c[0]} {c[1]} {c[2]} {c[3]} {c[4]} | {c[5]}")
+
+print(f"# {kname}<N>, gfx950, hipcc -O3 -ffp-contract=off: -Rpass-analysis=kernel-resource-usage per N, and the walk loop")
+print("# (the innermost loop holding 2(6N-2) fp64 VALU instructions: one odd + one even Gray step) scanned in the -S output.")
+print("# N waves/SIMD VGPRs AGPRs SGPRs spilled_VGPRs spilled_SGPRs scratch_bytes | loop: f64_insts scratch_insts "
+      "accvgpr_moves v_mov readlane/writelane | kernel_scratch_insts")
+for n in sorted(rows):
+    print(rows[n])
+bad = [n for n in sorted(rows) if not re.search(rf"\| {2 * (6 * n - 2)} 0 ", rows[n]) or rows[n].split()[5] != "0"
+       or rows[n].split()[7] != "0"]
+print(f"# condition (0 spilled VGPRs, 0 scratch bytes, loop = 2(6N-2) fp64 instructions, no scratch in it): "
+      f"{'holds at every N' if not bad else 'FAILS at N = ' + ', '.join(map(str, bad))}")

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SUP_ABI_VERSION 12  /* 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
+#define SUP_ABI_VERSION 13  /* 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SUP_OK            0
@@ -143,7 +143,9 @@ typedef struct {
   double   jit_ms;          /* hiprtc compile time spent by this call (0 when cached / unused)   */
   int      items_resumed;   /* queue items taken from sup_opts.checkpoint instead of walked      */
   int16_t  seg_cached_bits; /* segmented walk (walk_kind 3): cached walk bits of the plan run    */
-  int16_t  seg_pair_bits;   /* segmented walk: specialised pair bits (0 for other walks)          */
+  int16_t  seg_pair_bits;   /* segmented walk: specialised pair bits (0 for other walks);
+                               sup_perman_exact, sup_perman_exact_range: G, the rows the residue
+                               walk multiplies exactly before each reduction (1, 2 or 4)         */
 } sup_stats;
 
 /* Fill `o` with defaults. */
@@ -257,9 +259,44 @@ int sup_perman_cpu(const void* mat, sup_dtype t, int n, sup_kernel kernel, int t
  * host threads) takes items too; on_cpu = 1 runs o->threads host threads
  * instead.  The result never depends on who took which item (residue sums).
  * st (optional): kernel_ms (max over devices), wall_ms, devices_used,
- * gray_steps, chunks_done_cpu. */
+ * gray_steps, chunks_done_cpu, lane_bits, walk_bits, walk_kind (0 the dense
+ * residue kernel, 1 the prefix-blocked one: whichever the planner ran) and
+ * seg_pair_bits = G, its exact group size. */
 int sup_perman_exact(const void* mat, sup_dtype t, int n, const sup_opts* o, int on_cpu, char* out,
                      size_t out_len, sup_stats* st);
+
+/* Wave-chunks [c0, c1) of sup_perman_exact's walk (ABI 13): per prime, the sum
+ * of the terms (-1)^|S| prod_j X_j(S) of the doubled matrix 2A over the
+ * range's subsets, in [0, p).  The plan is sup_perman_exact's plan of 2A with
+ * the default layout, or o->walk_log2 walk bits when non-zero (m =
+ * min(walk_log2, n - 1 - lane_bits); walk_log2 outside [0, 31]: SUP_EINVAL);
+ * it has 2^(n-1-lane_bits-walk_bits) chunks.  Chunk a covers the subsets S of
+ * engine bits whose bits >= lane_bits + walk_bits are gray(a) = a ^ (a >> 1)
+ * and whose low bits are arbitrary; engine bit e is matrix column colmap[e]
+ * (colmap: optional, n - 1 ints), and X_j(S) = 2 a_j,n-1 - sum_c a_jc +
+ * 2 sum_{e in S} a_j,colmap[e].  The whole range, times 4(n&1) - 2, divided by
+ * 2^(n-1), is the permanent; residues of disjoint ranges add modulo p.
+ * form: 0 the planner's choice as in sup_perman_exact, 1 the dense kernel with
+ * the greedy column order, 2 the prefix-blocked kernel with that order (no
+ * chunk-end search; SUP_EINVAL when the layout has no walk bits, n <= 7).
+ * group: 0 the cost model's choice, or G = 1, 2, 4 rows multiplied exactly
+ * before each reduction.  The primes are sup_perman_exact's for that G: the
+ * largest below 2^pbits, pbits = min(42, 51 - G xbits), row sums of |a| below
+ * 2^xbits, until their product exceeds 8 |T|'s bound; a G whose pbits is
+ * below 20 is SUP_EINVAL (the message names xbits).
+ * primes, residues: cap entries each, *nprimes of them written; cap below the
+ * prime count is SUP_EINVAL before any walk (128 always suffice).  More than
+ * 8 primes take several launches.  One device (o->device_id; o->gpu_num is
+ * not used), or on_cpu = 1: o->threads host threads, the same residues.
+ * c0 > c1, c1 beyond the plan's chunks, a null matrix or output, n outside
+ * [1, 64]: SUP_EINVAL; c0 == c1: zeros.
+ * st: kernel_ms (summed over the launches), wall_ms, gray_steps = (c1 - c0)
+ * 2^(lane_bits + walk_bits), devices_used, lane_bits, walk_bits, walk_kind (0
+ * dense, 1 prefix-blocked: the kernel that ran), seg_pair_bits = G, leaves 1,
+ * est_ops_per_step (the plan's fp64 cost model). */
+int sup_perman_exact_range(const void* mat, sup_dtype t, int n, uint64_t c0, uint64_t c1, const sup_opts* o,
+                           int on_cpu, int form, int group, uint64_t* primes, uint64_t* residues, int cap,
+                           int* nprimes, int* colmap, sup_stats* st);
 
 /* The permanent in double-double (~106-bit significand): the MI355X form of
  * the reference's quad-precision calculation (v2 `-q`,
@@ -271,9 +308,27 @@ int sup_perman_exact(const void* mat, sup_dtype t, int n, const sup_opts* o, int
  * on_cpu = 1 runs the same operations on o->threads host threads.  Chunk
  * partials are combined in one fixed pairwise order, so the result is
  * bit-identical for any device or thread count.  ~8x the fp64 walk's work
- * (16n + 13 fp64 ops per Gray step). */
+ * (16n + 13 fp64 ops per Gray step).  st: walk_kind is the kernel the planner
+ * ran (0 dense, 1 prefix-blocked), lane_bits, walk_bits, and est_ops_per_step
+ * comes from that plan (16n + 13 for the dense walk, scaled by the plan's
+ * share of the dense cost model for the prefix-blocked one). */
 int sup_perman_quad(const void* mat, sup_dtype t, int n, const sup_opts* o, int on_cpu, double* out_hi,
                     double* out_lo, sup_stats* st);
+
+/* Wave-chunks [c0, c1) of sup_perman_quad's walk (ABI 13): the double-double
+ * chunk partials of that range folded by the pairwise tree over c - c0 (an odd
+ * last element moves up as it is), NOT scaled by 4(n&1) - 2, as *out_hi +
+ * *out_lo (both required).  Plan and start vector are sup_perman_quad's, with
+ * o->walk_log2 walk bits when non-zero; chunks, colmap, form and the error
+ * cases as sup_perman_exact_range, with x_j(S) = a_j,n-1 - sum_c a_jc / 2 +
+ * sum_{e in S} a_j,colmap[e].  Aligned power-of-two ranges folded pairwise in
+ * order (double-double adds) reproduce the whole range's bits, and the whole
+ * range with form 0 and walk_log2 0, times 4(n&1) - 2, is sup_perman_quad's
+ * result bit for bit.  One device (o->device_id; o->gpu_num
+ * is not used) or on_cpu = 1: o->threads host threads, bit-identical.
+ * st: as sup_perman_exact_range's, est_ops_per_step as sup_perman_quad's. */
+int sup_perman_quad_range(const void* mat, sup_dtype t, int n, uint64_t c0, uint64_t c1, const sup_opts* o,
+                          int on_cpu, int form, double* out_hi, double* out_lo, int* colmap, sup_stats* st);
 
 /* The permanent of a complex fp64 matrix (ABI 11).  The reference refuses
  * complex input (revised_perman/main.cpp:1557); boson-sampling amplitudes are

@@ -20,7 +20,7 @@ from ._lib import (KERNEL_DENSE, KERNEL_SKIPPER, KERNEL_SPARYSER, LEAF_FN, SCHED
                    SCHED_STATIC, SupApproxResult, SupError, SupOpts, SupReduceOpts, SupStats)
 
 __all__ = [
-    "perman", "perman_cpu", "perman_complex", "perman_complex_range", "perman_complex_batch", "perman_complex_submatrices", "read_mtx_complex", "partial", "perman_shard", "plan_info", "plan_key", "prepare", "read_matrix", "read_mtx", "sort_order",
+    "perman", "perman_cpu", "perman_exact", "perman_exact_range", "perman_quad", "perman_quad_range", "perman_complex", "perman_complex_range", "perman_complex_batch", "perman_complex_submatrices", "read_mtx_complex", "partial", "perman_shard", "plan_info", "plan_key", "prepare", "read_matrix", "read_mtx", "sort_order",
     "skip_order", "compress", "decompose", "perman_reduced", "approx", "grid_graph", "ALGOS_APPROX",
     "nw_start", "device_count", "rccl_devices", "layout", "ShardCall", "SupError", "ALGOS_DENSE", "ALGOS_SPARSE",
     "gpu_perman64_xshared_coalescing_mshared",
@@ -197,6 +197,55 @@ def perman_quad(mat, gpu_num: int = 1, device_id: int = 0, cpu: bool = False, th
     _lib.check(lib.sup_perman_quad(a.ctypes.data, dt, n, C.byref(o), int(bool(cpu)), C.byref(hi), C.byref(lo),
                                    C.byref(st)), "perman_quad")
     return ((hi.value, lo.value), st.as_dict()) if return_stats else (hi.value, lo.value)
+
+
+def _range_info(st: SupStats, colmap: np.ndarray, n: int) -> dict:
+    return {"L": st.lane_bits, "m": st.walk_bits, "colmap": [int(c) for c in colmap[: n - 1]],
+            "walk_kind": st.walk_kind, "gray_steps": st.gray_steps, "kernel_ms": st.kernel_ms,
+            "devices_used": st.devices_used, "leaves": st.leaves, "est_ops_per_step": st.est_ops_per_step}
+
+
+def perman_exact_range(mat, c0: int, c1: int, cpu: bool = False, threads: int = 16, device_id: int = 0,
+                       walk_log2: int = 0, form: int = 0, group: int = 0, cap: int = 128):
+    """Wave-chunks [c0, c1) of perman_exact's walk of 2A (sup_perman_exact_range):
+    (residues, info).  residues[q] is the sum of the range's terms modulo
+    info["primes"][q], in [0, p); info also holds L, m, colmap (engine bit e =
+    matrix column colmap[e]), G (rows multiplied exactly before each
+    reduction) and walk_kind (0 the dense kernel, 1 the prefix-blocked one).
+    ``form``: 0 the planner's choice, 1 dense, 2 prefix-blocked; ``group``: 0
+    the cost model's G, or 1, 2, 4; ``walk_log2``: walk bits (0 = default
+    layout).  One device, or (cpu=True) host threads: the same residues."""
+    a, dt, n = _mat(mat)
+    lib = _lib.load()
+    o = _opts(device_id=device_id, threads=threads, walk_log2=walk_log2)
+    size = max(int(cap), 1)
+    primes, res = np.zeros(size, np.uint64), np.zeros(size, np.uint64)
+    colmap, np_out, st = np.zeros(max(n - 1, 1), np.int32), C.c_int(0), SupStats()
+    _lib.check(lib.sup_perman_exact_range(a.ctypes.data, dt, n, int(c0), int(c1), C.byref(o), int(bool(cpu)),
+                                          int(form), int(group), primes.ctypes.data, res.ctypes.data, int(cap),
+                                          C.byref(np_out), colmap.ctypes.data, C.byref(st)), "perman_exact_range")
+    info = _range_info(st, colmap, n)
+    info["primes"] = [int(p) for p in primes[: np_out.value]]
+    info["G"] = int(st.seg_pair_bits)
+    return [int(r) for r in res[: np_out.value]], info
+
+
+def perman_quad_range(mat, c0: int, c1: int, cpu: bool = False, threads: int = 16, device_id: int = 0,
+                      walk_log2: int = 0, form: int = 0):
+    """Wave-chunks [c0, c1) of perman_quad's walk (sup_perman_quad_range):
+    ((hi, lo), info), the double-double chunk partials folded pairwise over
+    c - c0 and not scaled by 4(n&1)-2.  info: L, m, colmap, walk_kind as
+    perman_exact_range's.  One device, or (cpu=True) host threads —
+    bit-identical."""
+    a, dt, n = _mat(mat)
+    lib = _lib.load()
+    o = _opts(device_id=device_id, threads=threads, walk_log2=walk_log2)
+    hi, lo, st = C.c_double(0.0), C.c_double(0.0), SupStats()
+    colmap = np.zeros(max(n - 1, 1), np.int32)
+    _lib.check(lib.sup_perman_quad_range(a.ctypes.data, dt, n, int(c0), int(c1), C.byref(o), int(bool(cpu)),
+                                         int(form), C.byref(hi), C.byref(lo), colmap.ctypes.data, C.byref(st)),
+               "perman_quad_range")
+    return (hi.value, lo.value), _range_info(st, colmap, n)
 
 
 def _cmat(mat) -> tuple[np.ndarray, int]:

@@ -34,7 +34,8 @@ SCHED_SINGLE, SCHED_STATIC, SCHED_CHUNKS, SCHED_MANUAL = 0, 1, 2, 3
 EXPORTS = [
     "sup_opts_init", "sup_abi_version", "sup_last_error", "sup_device_count", "sup_rccl_devices", "sup_device_checks", "sup_device_warmup", "sup_kernel_time",
     "sup_perman", "sup_partial", "sup_perman_cpu", "sup_nw_start", "sup_perman_shard", "sup_plan_info",
-    "sup_prepare", "sup_plan_key", "sup_perman_exact", "sup_perman_reduced_exact", "sup_perman_quad",
+    "sup_prepare", "sup_plan_key", "sup_perman_exact", "sup_perman_exact_range", "sup_perman_reduced_exact",
+    "sup_perman_quad", "sup_perman_quad_range",
     "sup_perman_reduced_quad", "sup_perman_complex", "sup_perman_complex_range", "sup_read_mtx_complex",
     "sup_perman_complex_batch", "sup_perman_complex_submatrices",
     "sup_gpu_perman64_xshared_coalescing_mshared",
@@ -131,7 +132,7 @@ def load() -> C.CDLL:
             build()
         lib = C.CDLL(LIB_PATH)
         _declare(lib)
-        if lib.sup_abi_version() != 12:
+        if lib.sup_abi_version() != 13:
             raise RuntimeError("libsuperman_hip.so ABI version mismatch")
         _lib = lib
         return lib
@@ -155,6 +156,10 @@ def _declare(lib: C.CDLL) -> None:
     lib.sup_perman_cpu.argtypes = [P, I, I, I, I, C.POINTER(D), C.POINTER(SupStats)]
     lib.sup_perman_exact.argtypes = [P, I, I, C.POINTER(SupOpts), I, C.c_char_p, C.c_size_t, C.POINTER(SupStats)]
     lib.sup_perman_quad.argtypes = [P, I, I, C.POINTER(SupOpts), I, C.POINTER(D), C.POINTER(D), C.POINTER(SupStats)]
+    lib.sup_perman_exact_range.argtypes = [P, I, I, C.c_uint64, C.c_uint64, C.POINTER(SupOpts), I, I, I, P, P, I,
+                                           C.POINTER(I), P, C.POINTER(SupStats)]
+    lib.sup_perman_quad_range.argtypes = [P, I, I, C.c_uint64, C.c_uint64, C.POINTER(SupOpts), I, I, C.POINTER(D),
+                                          C.POINTER(D), P, C.POINTER(SupStats)]
     lib.sup_perman_complex.argtypes = [P, I, C.POINTER(SupOpts), I, C.POINTER(D), C.POINTER(D), C.POINTER(SupStats)]
     lib.sup_perman_complex_range.argtypes = [P, I, C.c_uint64, C.c_uint64, C.POINTER(SupOpts), I, C.POINTER(D),
                                              C.POINTER(D), C.POINTER(SupStats)]

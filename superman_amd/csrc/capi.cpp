@@ -123,16 +123,7 @@ int sup_nw_start(const void* mat, sup_dtype t, int n, double* x0, double* p0) {
 }
 
 // The default layout, or the walk length (m walk bits) sup_opts::walk_log2 asks for.
-static Layout layout_for(int n, const sup_opts& o) {
-  Layout lay = default_layout(n);
-  if (o.walk_log2 > 0) {
-    const int rest = n - 1 - lay.L;
-    lay.m = std::min(o.walk_log2, rest);
-    lay.h = rest - lay.m;
-    lay.fixed = true;
-  }
-  return lay;
-}
+static Layout layout_for(int n, const sup_opts& o) { return layout_with_walk(n, o.walk_log2); }
 
 int sup_perman(const void* mat, sup_dtype t, int n, sup_kernel kernel, sup_sched sched, const sup_opts* o_in,
                double* out, sup_stats* st) {
@@ -271,7 +262,8 @@ int sup_perman_exact(const void* mat, sup_dtype t, int n, const sup_opts* o_in, 
   std::string s;
   double kms = 0.0;
   int used = 0, cpu_items = 0;
-  if ((rc = exact_perman(A.data(), n, o, on_cpu != 0, s, &kms, &used, &cpu_items))) return rc;
+  RangeInfo ri;  // stays zero (dense, no walk bits) when a zero row ends the call early
+  if ((rc = exact_perman(A.data(), n, o, on_cpu != 0, s, &kms, &used, &cpu_items, &ri))) return rc;
   if (s.size() + 1 > out_len) {
     set_error("sup_perman_exact: output buffer too small");
     return SUP_EINVAL;
@@ -285,8 +277,50 @@ int sup_perman_exact(const void* mat, sup_dtype t, int n, const sup_opts* o_in, 
     st->visited_steps = st->gray_steps;
     st->devices_used = used;
     st->chunks_done_cpu = cpu_items;
-    st->walk_kind = (int)kWalkDense;
+    st->lane_bits = ri.lay.L;
+    st->walk_bits = ri.lay.m;
+    st->walk_kind = ri.walk_kind;
+    st->seg_pair_bits = (int16_t)ri.group;
     st->leaves = 1;
+  }
+  return SUP_OK;
+}
+
+int sup_perman_exact_range(const void* mat, sup_dtype t, int n, uint64_t c0, uint64_t c1, const sup_opts* o_in,
+                           int on_cpu, int form, int group, uint64_t* primes, uint64_t* residues, int cap,
+                           int* nprimes, int* colmap, sup_stats* st) {
+  auto t0 = std::chrono::steady_clock::now();
+  if (!mat || !primes || !residues || !nprimes) {
+    set_error("sup_perman_exact_range: null matrix or output pointer");
+    return SUP_EINVAL;
+  }
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  int rc = check_range_request(n, o, form, "sup_perman_exact_range");
+  if (rc) return rc;
+  std::vector<double> A;
+  if ((rc = to_double(mat, t, n, A))) return rc;
+  std::vector<uint64_t> pr, res;
+  RangeInfo ri;
+  if ((rc = exact_perman_range(A.data(), n, c0, c1, o, on_cpu != 0, form, group, cap, pr, res, &ri))) return rc;
+  std::copy(pr.begin(), pr.end(), primes);
+  std::copy(res.begin(), res.end(), residues);
+  *nprimes = (int)pr.size();
+  if (colmap) std::copy(ri.colmap.begin(), ri.colmap.end(), colmap);
+  if (st) {
+    std::memset(st, 0, sizeof(*st));
+    st->kernel_ms = ri.kernel_ms;
+    st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    st->gray_steps = (c1 - c0) << (ri.lay.L + ri.lay.m);
+    st->visited_steps = st->gray_steps;
+    st->devices_used = ri.devices;
+    st->lane_bits = ri.lay.L;
+    st->walk_bits = ri.lay.m;
+    st->walk_kind = ri.walk_kind;
+    st->seg_pair_bits = (int16_t)ri.group;
+    st->leaves = 1;
+    st->est_ops_per_step = ri.est_ops;
   }
   return SUP_OK;
 }
@@ -306,7 +340,8 @@ int sup_perman_quad(const void* mat, sup_dtype t, int n, const sup_opts* o_in, i
   else sup_opts_init(&o);
   double hi = 0.0, lo = 0.0, kms = 0.0;
   int used = 0;
-  if ((rc = quad_perman(A.data(), n, o, on_cpu != 0, &hi, &lo, &kms, &used))) return rc;
+  RangeInfo ri;
+  if ((rc = quad_perman(A.data(), n, o, on_cpu != 0, &hi, &lo, &kms, &used, &ri))) return rc;
   *out_hi = hi;
   if (out_lo) *out_lo = lo;
   if (st) {
@@ -316,9 +351,47 @@ int sup_perman_quad(const void* mat, sup_dtype t, int n, const sup_opts* o_in, i
     st->gray_steps = 1ull << (n - 1);
     st->visited_steps = st->gray_steps;
     st->devices_used = used;
-    st->walk_kind = (int)kWalkDense;
+    st->lane_bits = ri.lay.L;
+    st->walk_bits = ri.lay.m;
+    st->walk_kind = ri.walk_kind;
     st->leaves = 1;
-    st->est_ops_per_step = 16.0 * n + 13.0;
+    st->est_ops_per_step = ri.est_ops;
+  }
+  return SUP_OK;
+}
+
+int sup_perman_quad_range(const void* mat, sup_dtype t, int n, uint64_t c0, uint64_t c1, const sup_opts* o_in,
+                          int on_cpu, int form, double* out_hi, double* out_lo, int* colmap, sup_stats* st) {
+  auto t0 = std::chrono::steady_clock::now();
+  if (!mat || !out_hi || !out_lo) {
+    set_error("sup_perman_quad_range: null matrix or output pointer");
+    return SUP_EINVAL;
+  }
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  int rc = check_range_request(n, o, form, "sup_perman_quad_range");
+  if (rc) return rc;
+  std::vector<double> A;
+  if ((rc = to_double(mat, t, n, A))) return rc;
+  double hi = 0.0, lo = 0.0;
+  RangeInfo ri;
+  if ((rc = quad_perman_range(A.data(), n, c0, c1, o, on_cpu != 0, form, &hi, &lo, &ri))) return rc;
+  *out_hi = hi;
+  *out_lo = lo;
+  if (colmap) std::copy(ri.colmap.begin(), ri.colmap.end(), colmap);
+  if (st) {
+    std::memset(st, 0, sizeof(*st));
+    st->kernel_ms = ri.kernel_ms;
+    st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    st->gray_steps = (c1 - c0) << (ri.lay.L + ri.lay.m);
+    st->visited_steps = st->gray_steps;
+    st->devices_used = ri.devices;
+    st->lane_bits = ri.lay.L;
+    st->walk_bits = ri.lay.m;
+    st->walk_kind = ri.walk_kind;
+    st->leaves = 1;
+    st->est_ops_per_step = ri.est_ops;
   }
   return SUP_OK;
 }

@@ -120,16 +120,7 @@ cx cx_pairwise(const double* parts, uint64_t count) {
 
 // The layout of a complex walk of order n: the default layout, or o.walk_log2
 // walk bits (n in [1, 64], o.walk_log2 in [0, 31]).
-Layout cplx_layout(int n, const sup_opts& o) {
-  Layout lay = default_layout(n);
-  if (o.walk_log2 > 0) {
-    const int rest = n - 1 - lay.L;
-    lay.m = std::min(o.walk_log2, rest);
-    lay.h = rest - lay.m;
-    lay.fixed = true;
-  }
-  return lay;
-}
+Layout cplx_layout(int n, const sup_opts& o) { return layout_with_walk(n, o.walk_log2); }
 
 // The plan (column planes Re, Im in P.cols) and start vector of A, n x n
 // row-major interleaved (re, im).

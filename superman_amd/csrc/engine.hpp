@@ -47,6 +47,9 @@ struct Layout {
   uint64_t chunks() const { return 1ull << h; }
 };
 Layout default_layout(int n);
+// The default layout, or (walk_log2 > 0) m = min(walk_log2, n - 1 - L) walk
+// bits asked for by the caller (sup_opts::walk_log2, checked to be in [0, 31]).
+Layout layout_with_walk(int n, int walk_log2);
 
 // Product tree of the segmented walk (jit.cpp make_tree).  Items are engine
 // rows (item_row[t] = row) and, when tail_hi > tail_lo, one constant item
@@ -404,8 +407,30 @@ void cpu_exact_range(const Plan& P, uint64_t c0, uint64_t c1, const std::vector<
 // Exact permanent of integer-valued A as a decimal string (sup_perman_exact).
 // Several devices or o.cpu_worker: a queue of chunk items; *cpu_items = items
 // the CPU worker took.
+// What an exact or double-double call reports beside its value (sup_stats):
+// the plan that ran.
+struct RangeInfo {
+  double kernel_ms = 0.0, est_ops = 0.0;  // est_ops: the plan's cost model (walk_cost; quad: in double-double ops)
+  int devices = 0;
+  int walk_kind = 0;  // the plan's kind: kWalkDense or kWalkSparse (the prefix-blocked kernel)
+  int group = 0;      // exact walk: rows per exact group product (1, 2, 4)
+  Layout lay{};
+  std::vector<int> colmap;  // range entries: Plan::colmap
+};
 int exact_perman(const double* A, int n, const sup_opts& o, bool on_cpu, std::string& out, double* kernel_ms,
-                 int* devices_used, int* cpu_items = nullptr);
+                 int* devices_used, int* cpu_items = nullptr, RangeInfo* info = nullptr);
+// n in [1, 64], o.walk_log2 in [0, 31] and form in [0, 2] of a range entry
+// (`who` in the messages), else SUP_EINVAL.
+int check_range_request(int n, const sup_opts& o, int form, const char* who);
+// Per prime, the sum of the terms of wave-chunks [c0, c1) of exact_perman's
+// plan of 2A (o.walk_log2 honoured) in [0, p), with exact_perman's primes for
+// the group size that runs (sup_perman_exact_range); one device (o.device_id),
+// kMaxPrimes per launch, or host threads.  form: 0 the planner's choice, 1 the
+// dense kernel, 2 the prefix-blocked kernel; group: 0 the cost model's, or 1,
+// 2, 4.  More than `cap` primes: SUP_EINVAL before any walk.
+int exact_perman_range(const double* A, int n, uint64_t c0, uint64_t c1, const sup_opts& o, bool on_cpu, int form,
+                       int group, int cap, std::vector<uint64_t>& primes, std::vector<uint64_t>& res,
+                       RangeInfo* info);
 // The same after the -o reductions (sup_perman_reduced_exact): exact leaves, big-integer sum.
 int exact_perman_reduced(const double* A, int n, const sup_opts& o, bool on_cpu, const sup_reduce_opts& r,
                          std::string& out, double* kernel_ms, int* leaves);
@@ -444,7 +469,13 @@ int decompose_dd_batched(const double* A, int n, const sup_reduce_opts& r, int w
                          const std::function<int(int, const double*, int, dd*)>& leaf, dd* out, int* n_leaves);
 // Permanent in double-double (sup_perman_quad): *hi + *lo.
 int quad_perman(const double* A, int n, const sup_opts& o, bool on_cpu, double* hi, double* lo, double* kernel_ms,
-                int* devices_used);
+                int* devices_used, RangeInfo* info = nullptr);
+// The dd_pairwise fold of the chunk partials of wave-chunks [c0, c1) of
+// quad_perman's plan and start vector (o.walk_log2 honoured), not scaled by
+// 4(n&1) - 2 (sup_perman_quad_range); one device (o.device_id) or host
+// threads.  form as exact_perman_range's.
+int quad_perman_range(const double* A, int n, uint64_t c0, uint64_t c1, const sup_opts& o, bool on_cpu, int form,
+                      double* hi, double* lo, RangeInfo* info);
 
 // ---- complex fp64 walk (cplx.cpp, walk_cplx.hip) ----
 // Wave-chunk partials (re, im) of chunks [c0, c1) of the complex plan P — a

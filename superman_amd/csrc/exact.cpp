@@ -13,6 +13,9 @@
 //     (Garner) into the exact integer T, |T| <= 2^(n-1) prod_j rowabs_j <
 //     (prod p) / 2, and perm = (4(n&1) - 2) T / 2^n.  T must be divisible by
 //     2^(n-1): that is checked, a free self-test of the whole computation.
+// sup_perman_exact_range returns the residues of a range of wave-chunks of the
+// same walk (same checks, G, primes and plan: exact_setup), with the kernel
+// and G forced on request, so every compiled instance can be run on its own.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -148,10 +151,23 @@ struct Big {
   }
 };
 
-}  // namespace
+// What both exact entries decide before they walk: the group size G (| 8 for
+// the blocked kernel, run_range_exact's code), the primes and the plan of 2A.
+struct ExactSetup {
+  bool zero_row = false;  // a row of zeros (whole = true only): the permanent is 0, nothing else is filled
+  int group = 0;
+  std::vector<double> primes;
+  Plan P;
+};
 
-int exact_perman(const double* A, int n, const sup_opts& o, bool on_cpu, std::string& out, double* kernel_ms,
-                 int* devices_used, int* cpu_items) {
+// The front half of sup_perman_exact and sup_perman_exact_range (`who` in
+// messages).  whole: sup_perman_exact, which stops at a zero row; the range
+// entry walks such a matrix like any other (every term is zero).  form: 0 the
+// planner's choice, 1 the dense kernel with the greedy column order, 2 the
+// prefix-blocked kernel with it.  want_group: 0 the cost model's G, or 1, 2, 4.
+int exact_setup(const double* A, int n, const Layout& lay, bool whole, int form, int want_group, const char* who,
+                ExactSetup& S) {
+  const std::string name(who);
   // integrality and size
   double maxrow = 0.0, logT = n - 1;
   for (int j = 0; j < n; ++j) {
@@ -159,17 +175,17 @@ int exact_perman(const double* A, int n, const sup_opts& o, bool on_cpu, std::st
     for (int c = 0; c < n; ++c) {
       const double v = A[(size_t)j * n + c];
       if (v != std::floor(v) || std::fabs(v) >= 2147483648.0) {
-        set_error("sup_perman_exact: entries must be integers with |a| < 2^31");
+        set_error(name + ": entries must be integers with |a| < 2^31");
         return SUP_EINVAL;
       }
       ra += std::fabs(v);
     }
     if (ra == 0.0) {  // a zero row: the permanent is 0
-      out = "0";
-      if (kernel_ms) *kernel_ms = 0.0;
-      if (devices_used) *devices_used = 0;
-      if (cpu_items) *cpu_items = 0;
-      return SUP_OK;
+      if (whole) {
+        S.zero_row = true;
+        return SUP_OK;
+      }
+      continue;
     }
     maxrow = std::max(maxrow, ra);
     logT += std::log2(ra);
@@ -181,27 +197,40 @@ int exact_perman(const double* A, int n, const sup_opts& o, bool on_cpu, std::st
   // (n (1 - 1/G) per step) against chain length (4 n / G per prime) and
   // smaller primes (more of them).
   const int xbits = (int)std::ceil(std::log2(maxrow + 1.0));
+  auto pbits_of = [xbits](int G) { return std::min(42, 52 - G * xbits - 1); };
   int group = 0, pbits = 0;
-  double best = 1e300;
-  for (int G : {1, 2, 4}) {
-    const int pb = std::min(42, 52 - G * xbits - 1);
-    if (pb < 20) continue;
-    const double primes_needed = std::ceil((logT + 3.0) / (pb - 0.5));
-    const double ops = n * (1.0 - 1.0 / G) + primes_needed * (4.0 * std::ceil((double)n / G) + 3.0);
-    if (ops < best) best = ops, group = G, pbits = pb;
-  }
-  if (group == 0) {
-    set_error("sup_perman_exact: row sums of |a| must stay below 2^31 for the residue walk");
-    return SUP_EUNSUPPORTED;
+  if (want_group) {
+    if (want_group != 1 && want_group != 2 && want_group != 4) {
+      set_error(name + ": group = " + std::to_string(want_group) + " (0 = the planner's choice, or 1, 2, 4)");
+      return SUP_EINVAL;
+    }
+    group = want_group, pbits = pbits_of(want_group);
+    if (pbits < 20) {
+      set_error(name + ": group = " + std::to_string(want_group) + " with xbits = " + std::to_string(xbits) +
+                " (row sums of |a| below 2^xbits) leaves primes of " + std::to_string(pbits) +
+                " bits; at least 20 are needed (52 - group xbits - 1)");
+      return SUP_EINVAL;
+    }
+  } else {
+    double best = 1e300;
+    for (int G : {1, 2, 4}) {
+      const int pb = pbits_of(G);
+      if (pb < 20) continue;
+      const double primes_needed = std::ceil((logT + 3.0) / (pb - 0.5));
+      const double ops = n * (1.0 - 1.0 / G) + primes_needed * (4.0 * std::ceil((double)n / G) + 3.0);
+      if (ops < best) best = ops, group = G, pbits = pb;
+    }
+    if (group == 0) {
+      set_error(name + ": row sums of |a| must stay below 2^31 for the residue walk");
+      return SUP_EUNSUPPORTED;
+    }
   }
   // primes: the largest below 2^pbits, until their product exceeds 2 |T| (+ margin)
-  std::vector<double> primes;
   double bits = 0.0;
   for (uint64_t c = (1ull << pbits) - 1; bits < logT + 2.0 + 1.0; c -= 2)
-    if (is_prime(c)) primes.push_back((double)c), bits += std::log2((double)c);
-  const int np = (int)primes.size();
+    if (is_prime(c)) S.primes.push_back((double)c), bits += std::log2((double)c);
 
-  Plan P;
+  Plan& P = S.P;
   std::vector<double> A2((size_t)n * n);
   for (size_t i = 0; i < A2.size(); ++i) A2[i] = 2.0 * A[i];
   // The prefix-blocked walk (walk_exact_blocked: rows in first-touch order,
@@ -210,18 +239,126 @@ int exact_perman(const double* A, int n, const sup_opts& o, bool on_cpu, std::st
   // else the dense walk with its walk + lane columns in the greedy prefix
   // order.  Either way the rows no walk or lane column touches end the chunks
   // where they are exactly zero (walk_exact.hip), and any column order gives
-  // the same exact sum.
-  const Layout lay = default_layout(n);
+  // the same exact sum.  A forced blocked form takes the greedy prefix order
+  // as it is (no chunk-end search).
   int rc = SUP_OK;
-  if (lay.m > 0 && (rc = make_plan(A2.data(), n, kWalkSparse, false, lay, P)) == SUP_OK &&
-      walk_cost(P) < 2.0 * n + 1.0 && (rc = improve_sparse_plan(A2.data(), n, lay, P)) == SUP_OK) {
+  if (form == 2) {
+    if (lay.m == 0) {
+      set_error(name + ": form 2 (the prefix-blocked kernel) needs walk bits, this layout has m = 0");
+      return SUP_EINVAL;
+    }
+    rc = make_plan(A2.data(), n, kWalkSparse, false, lay, P);
+    group |= 8;
+  } else if (form == 0 && lay.m > 0 && (rc = make_plan(A2.data(), n, kWalkSparse, false, lay, P)) == SUP_OK &&
+             walk_cost(P) < 2.0 * n + 1.0 && (rc = improve_sparse_plan(A2.data(), n, lay, P)) == SUP_OK) {
     group |= 8;  // run_range_exact / walk_exact.hip: the blocked kernel
   } else {
     SegChoice order;
     order.order = greedy_walk_order(A2.data(), n, lay.m + lay.L);
     rc = make_plan(A2.data(), n, kWalkDense, false, lay, P, lay.m > 0 ? &order : nullptr);
   }
+  S.group = group;
+  return rc;
+}
+
+}  // namespace
+
+int check_range_request(int n, const sup_opts& o, int form, const char* who) {
+  if (n < 1 || n > SUP_MAX_N) {
+    set_error(std::string(who) + ": n = " + std::to_string(n) + " outside [1, 64] (64-bit Gray index)");
+    return SUP_EINVAL;
+  }
+  if (o.walk_log2 < 0 || o.walk_log2 > 31) {
+    set_error(std::string(who) + ": walk_log2 = " + std::to_string(o.walk_log2) +
+              " outside [0, 31] (0 = default layout)");
+    return SUP_EINVAL;
+  }
+  if (form < 0 || form > 2) {
+    set_error(std::string(who) + ": form = " + std::to_string(form) +
+              " (0 = the planner's choice, 1 dense, 2 prefix-blocked)");
+    return SUP_EINVAL;
+  }
+  return SUP_OK;
+}
+
+int exact_perman_range(const double* A, int n, uint64_t c0, uint64_t c1, const sup_opts& o, bool on_cpu, int form,
+                       int group, int cap, std::vector<uint64_t>& primes, std::vector<uint64_t>& res,
+                       RangeInfo* info) {
+  const char* who = "sup_perman_exact_range";
+  int rc = check_range_request(n, o, form, who);
   if (rc) return rc;
+  ExactSetup S;
+  if ((rc = exact_setup(A, n, layout_with_walk(n, o.walk_log2), false, form, group, who, S))) return rc;
+  const Plan& P = S.P;
+  if (c0 > c1 || c1 > P.lay.chunks()) {
+    set_error("wave-chunk range [c0, c1) must satisfy c0 <= c1 <= " + std::to_string(P.lay.chunks()) +
+              " (the plan's chunks)");
+    return SUP_EINVAL;
+  }
+  const int np = (int)S.primes.size();
+  if (cap < np) {  // before any walk
+    set_error(std::string(who) + ": cap = " + std::to_string(cap) + " but this walk has " + std::to_string(np) +
+              " primes");
+    return SUP_EINVAL;
+  }
+  primes.resize(np);
+  for (int q = 0; q < np; ++q) primes[q] = (uint64_t)S.primes[q];
+  res.assign(np, 0);
+  RangeInfo ri;
+  ri.lay = P.lay;
+  ri.walk_kind = (int)P.kind;
+  ri.group = S.group & 7;
+  ri.colmap = P.colmap;
+  ri.est_ops = walk_cost(P);
+  if (on_cpu) {
+    cpu_exact_range(P, c0, c1, S.primes, std::max(o.threads, 1), res);
+  } else {
+    int ndev = 0;
+    if ((rc = device_count(&ndev))) return rc;
+    if (ndev == 0) {
+      set_error(std::string("no HIP device available (") + who + " has no CPU fallback; on_cpu = 1 runs host threads)");
+      return SUP_ENODEV;
+    }
+    if (o.device_id < 0 || o.device_id >= ndev) {
+      set_error(std::string(who) + ": device_id out of range");
+      return SUP_EINVAL;
+    }
+    for (int q0 = 0; q0 < np; q0 += kMaxPrimes) {  // kMaxPrimes per launch
+      const std::vector<double> pr(S.primes.begin() + q0, S.primes.begin() + std::min(np, q0 + kMaxPrimes));
+      std::vector<uint64_t> r;
+      double ms = 0.0;
+      if ((rc = run_range_exact(o.device_id, P, S.group, c0, c1, pr, r, &ms))) return rc;
+      std::copy(r.begin(), r.end(), res.begin() + q0);
+      ri.kernel_ms += ms;
+    }
+    ri.devices = 1;
+  }
+  if (info) *info = std::move(ri);
+  return SUP_OK;
+}
+
+int exact_perman(const double* A, int n, const sup_opts& o, bool on_cpu, std::string& out, double* kernel_ms,
+                 int* devices_used, int* cpu_items, RangeInfo* info) {
+  ExactSetup S;
+  int rc = exact_setup(A, n, default_layout(n), true, 0, 0, "sup_perman_exact", S);
+  if (rc) return rc;
+  if (S.zero_row) {
+    out = "0";
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (devices_used) *devices_used = 0;
+    if (cpu_items) *cpu_items = 0;
+    return SUP_OK;
+  }
+  const int group = S.group;
+  const std::vector<double>& primes = S.primes;
+  const int np = (int)primes.size();
+  const Plan& P = S.P;
+  if (info) {
+    info->lay = P.lay;
+    info->walk_kind = (int)P.kind;
+    info->group = group & 7;
+    info->est_ops = walk_cost(P);
+  }
   const uint64_t C = P.lay.chunks();
 
   // residues of T, per prime.  One device: its whole range, kMaxPrimes per

@@ -106,6 +106,17 @@ Layout default_layout(int n) {
   return l;
 }
 
+Layout layout_with_walk(int n, int walk_log2) {
+  Layout lay = default_layout(n);
+  if (walk_log2 > 0) {
+    const int rest = n - 1 - lay.L;
+    lay.m = std::min(walk_log2, rest);
+    lay.h = rest - lay.m;
+    lay.fixed = true;
+  }
+  return lay;
+}
+
 // Walk-column order that keeps the row prefixes small: the first column is
 // tried exhaustively, the rest is greedy (fewest newly covered rows, then
 // fewest nonzeros, then lowest index); the order with the lowest prefix cost

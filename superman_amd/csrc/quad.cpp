@@ -12,9 +12,14 @@
 // partials are bit-identical.  They are combined on the host in one fixed
 // pairwise tree over the global chunk index, so the result does not depend on
 // the device count, the split or the host thread count.
+// sup_perman_quad_range folds the partials of a range of wave-chunks of the
+// same walk (same plan and start vector: quad_setup), with o.walk_log2 walk
+// bits and the kernel forced on request.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <new>
+#include <stdexcept>
 #include <string>
 #include <thread>
 
@@ -161,9 +166,14 @@ void cpu_dd_range(const Plan& P, const std::vector<double>& x0dd, uint64_t c0, u
   for (auto& t : th) t.join();
 }
 
-int quad_perman(const double* A, int n, const sup_opts& o, bool on_cpu, double* hi, double* lo, double* kernel_ms,
-                int* devices_used) {
-  Plan P;
+namespace {
+
+// The front half of sup_perman_quad and sup_perman_quad_range: the plan and
+// the double-double start vector.  form: 0 the planner's choice, 1 the dense
+// kernel with the greedy column order, 2 the prefix-blocked kernel with it
+// (no chunk-end search).
+int quad_setup(const double* A, int n, const Layout& lay, int form, const char* who, Plan& P,
+               std::vector<double>& x0dd) {
   // The prefix-blocked walk (walk_dd_blocked) when its cost model beats the
   // dense walk's, else the dense walk with its walk + lane columns in the
   // greedy prefix order; the rows none of them touches end the chunks where
@@ -173,18 +183,23 @@ int quad_perman(const double* A, int n, const sup_opts& o, bool on_cpu, double* 
   // (n = 40, modelled 45.5 against 81 ops) ran 12.0 s blocked against 9.9 s
   // dense, d = 0.2 and dwt_59's n = 30 leaves (~0.25-0.3 of the dense ops)
   // faster blocked.
-  const Layout lay = default_layout(n);
   const double bar = (n <= 28 ? 1.0 : 0.4) * (2.0 * n + 1.0);
   int rc = SUP_OK;
-  if (!(lay.m > 0 && (rc = make_plan(A, n, kWalkSparse, false, lay, P)) == SUP_OK && walk_cost(P) < bar &&
-        (rc = improve_sparse_plan(A, n, lay, P)) == SUP_OK)) {
+  if (form == 2) {
+    if (lay.m == 0) {
+      set_error(std::string(who) + ": form 2 (the prefix-blocked kernel) needs walk bits, this layout has m = 0");
+      return SUP_EINVAL;
+    }
+    rc = make_plan(A, n, kWalkSparse, false, lay, P);
+  } else if (!(form == 0 && lay.m > 0 && (rc = make_plan(A, n, kWalkSparse, false, lay, P)) == SUP_OK &&
+               walk_cost(P) < bar && (rc = improve_sparse_plan(A, n, lay, P)) == SUP_OK)) {
     SegChoice order;
     order.order = greedy_walk_order(A, n, lay.m + lay.L);
     rc = make_plan(A, n, kWalkDense, false, lay, P, lay.m > 0 ? &order : nullptr);
   }
   if (rc) return rc;
   // Nijenhuis-Wilf start vector in double-double (rows in engine order)
-  std::vector<double> x0dd(2 * (size_t)P.NP, 0.0);
+  x0dd.assign(2 * (size_t)P.NP, 0.0);
   for (int j = 0; j < n; ++j) {
     const int i = P.rowperm[j];
     dd rs{0.0, 0.0};
@@ -192,6 +207,85 @@ int quad_perman(const double* A, int n, const sup_opts& o, bool on_cpu, double* 
     const dd x = dd_add_d(dd{-0.5 * rs.hi, -0.5 * rs.lo}, A[(size_t)i * n + n - 1]);
     x0dd[j] = x.hi, x0dd[P.NP + j] = x.lo;
   }
+  return SUP_OK;
+}
+
+// What the plan reports: est_ops in double-double terms, the dense walk's
+// 16n + 13 fp64 ops per Gray step scaled by the plan's share of the dense
+// fp64 model (walk_cost; 1 for the dense walk).
+void quad_info(const Plan& P, RangeInfo& ri) {
+  ri.lay = P.lay;
+  ri.walk_kind = (int)P.kind;
+  ri.est_ops = (16.0 * P.n + 13.0) * (walk_cost(P) / (2.0 * P.n + 1.0));
+}
+
+int quad_need_device(const sup_opts& o, const char* who, int* ndev) {
+  int rc = device_count(ndev);
+  if (rc) return rc;
+  if (*ndev == 0) {
+    set_error(std::string("no HIP device available (") + who + " has no CPU fallback; on_cpu = 1 runs host threads)");
+    return SUP_ENODEV;
+  }
+  if (o.device_id < 0 || o.device_id >= *ndev) {
+    set_error(std::string(who) + ": device_id out of range");
+    return SUP_EINVAL;
+  }
+  return SUP_OK;
+}
+
+}  // namespace
+
+int quad_perman_range(const double* A, int n, uint64_t c0, uint64_t c1, const sup_opts& o, bool on_cpu, int form,
+                      double* hi, double* lo, RangeInfo* info) {
+  const char* who = "sup_perman_quad_range";
+  int rc = check_range_request(n, o, form, who);
+  if (rc) return rc;
+  Plan P;
+  std::vector<double> x0dd;
+  if ((rc = quad_setup(A, n, layout_with_walk(n, o.walk_log2), form, who, P, x0dd))) return rc;
+  if (c0 > c1 || c1 > P.lay.chunks()) {
+    set_error("wave-chunk range [c0, c1) must satisfy c0 <= c1 <= " + std::to_string(P.lay.chunks()) +
+              " (the plan's chunks)");
+    return SUP_EINVAL;
+  }
+  const uint64_t count = c1 - c0;
+  std::vector<double> parts;
+  try {
+    parts.assign(2 * (size_t)count, 0.0);
+  } catch (const std::bad_alloc&) {
+    set_error("out of host memory for " + std::to_string(count) + " wave-chunk partials");
+    return SUP_ENOMEM;
+  } catch (const std::length_error&) {
+    set_error("out of host memory for " + std::to_string(count) + " wave-chunk partials");
+    return SUP_ENOMEM;
+  }
+  RangeInfo ri;
+  quad_info(P, ri);
+  ri.colmap = P.colmap;
+  if (on_cpu) {
+    cpu_dd_range(P, x0dd, c0, c1, std::max(o.threads, 1), parts.data());
+  } else {
+    int ndev = 0;
+    if ((rc = quad_need_device(o, who, &ndev))) return rc;
+    if ((rc = run_range_dd(o.device_id, P, x0dd, c0, c1, parts.data(), &ri.kernel_ms))) return rc;
+    ri.devices = 1;
+  }
+  std::vector<dd> v(count);
+  for (uint64_t a = 0; a < count; ++a) v[a] = dd{parts[2 * a], parts[2 * a + 1]};
+  const dd total = dd_pairwise(std::move(v));
+  *hi = total.hi;
+  *lo = total.lo;
+  if (info) *info = std::move(ri);
+  return SUP_OK;
+}
+
+int quad_perman(const double* A, int n, const sup_opts& o, bool on_cpu, double* hi, double* lo, double* kernel_ms,
+                int* devices_used, RangeInfo* info) {
+  Plan P;
+  std::vector<double> x0dd;
+  int rc = quad_setup(A, n, default_layout(n), 0, "sup_perman_quad", P, x0dd);
+  if (rc) return rc;
+  if (info) quad_info(P, *info);
   const uint64_t C = P.lay.chunks();
   std::vector<double> parts(2 * C, 0.0);
   double kms = 0.0;
@@ -200,15 +294,7 @@ int quad_perman(const double* A, int n, const sup_opts& o, bool on_cpu, double* 
     cpu_dd_range(P, x0dd, 0, C, std::max(o.threads, 1), parts.data());
   } else {
     int ndev = 0;
-    if ((rc = device_count(&ndev))) return rc;
-    if (ndev == 0) {
-      set_error("no HIP device available (sup_perman_quad has no CPU fallback; on_cpu = 1 runs host threads)");
-      return SUP_ENODEV;
-    }
-    if (o.device_id < 0 || o.device_id >= ndev) {
-      set_error("sup_perman_quad: device_id out of range");
-      return SUP_EINVAL;
-    }
+    if ((rc = quad_need_device(o, "sup_perman_quad", &ndev))) return rc;
     const int G = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::max(1, std::min(o.gpu_num, ndev - o.device_id)), C));
     std::vector<int> drc(G, SUP_OK);
     std::vector<double> dms(G, 0.0);

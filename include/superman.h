@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SUP_ABI_VERSION 13  /* 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
+#define SUP_ABI_VERSION 14  /* 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SUP_OK            0
@@ -399,6 +399,48 @@ int sup_perman_complex_batch(const double* mats, int n, uint64_t count, const su
 int sup_perman_complex_submatrices(const double* U, int R, int C, const int32_t* rows,
                                    const int32_t* cols, int n, uint64_t count, const sup_opts* o,
                                    int on_cpu, double* out, sup_stats* st);
+
+/* Collision-aware form of sup_perman_complex_submatrices (ABI 14): the same
+ * arguments, index checks and errors (it drops in where that call is used),
+ * but equal indices are not only gathered.  Equal indices on one side make
+ * equal columns (rows) of the gathered matrix A, and subsets that take the
+ * same number of copies from every group give the same term: with distinct
+ * columns b_k of multiplicities t_k (order of first appearance), one copy of
+ * the rarest group held (the first on a tie; t'_k = t_k - 1 there, t_k else),
+ *   per(A) = 2 sum_{0 <= v_k <= t'_k} (-1)^(sum v) prod_k C(t'_k, v_k) prod_j x_j(v),
+ *   x_j(v) = 1/2 sum_k (t_k - 2 v_k) b_k[j],
+ * T = prod (t'_k + 1) terms instead of 2^(n-1) (n = 24 with six groups of
+ * four: 12,500 instead of 8.4 million).  The side with the smaller T is
+ * collapsed (columns on a tie, the rows through the transposed gather); the
+ * other side stays expanded.  Without repeats T = 2^(n-1).
+ * Result k equals the permanent of gathered matrix k but does NOT have
+ * sup_perman_complex's (so sup_perman_complex_submatrices') bits: the sum, its
+ * order and its scale differ.  It is a function of (U, rows[k], cols[k]) only:
+ * bit-identical on the GPU (per slab three launches: tables and start
+ * vectors written on the device from U and the lists, walk_cplxf.hip over one
+ * queue of the wave-chunks of all its matrices, a per-matrix fold; the
+ * grouping is host work on o->threads threads), on any device count, for any
+ * slab size (256 MiB of tables and partials; the environment variable
+ * SUP_CPLX_FOCK_SLAB=<matrices> overrides it, for tests) and on o->threads
+ * host threads (on_cpu = 1).  o->gpu_num devices from o->device_id take
+ * contiguous ranges of matrices.  o->walk_log2 is checked as the submatrix
+ * entry checks it and otherwise unused: the layout is a function of the
+ * collapsed side's multiplicities alone.  A matrix with more
+ * than 2^24 wave-chunks (T above about 2^40): SUP_EUNSUPPORTED before any
+ * work.  No device with on_cpu = 0: SUP_ENODEV (no silent CPU fallback).
+ * st: leaves = count, gray_steps = count 2^(n-1) (nominal), visited_steps =
+ * sum_k T_k, kernel_ms (max over devices of the summed prepare, walk and fold
+ * kernel time), wall_ms, devices_used, grid, est_ops_per_step = 6n (per visited
+ * step: 2n column adds, 4(n-1) for the product, 4 for acc += w term). */
+int sup_perman_complex_fock(const double* U, int R, int C, const int32_t* rows,
+                            const int32_t* cols, int n, uint64_t count, const sup_opts* o,
+                            int on_cpu, double* out, sup_stats* st);
+/* What sup_perman_complex_fock would do with these lists, host only (no
+ * device): per matrix the terms T (terms[k]) and the side collapsed (side[k]:
+ * 0 columns, 1 rows).  Either output may be NULL.  Null lists or n outside
+ * [1, 64]: SUP_EINVAL.  Indices are only compared, not range-checked. */
+int sup_perman_complex_fock_plan(const int32_t* rows, const int32_t* cols, int n,
+                                 uint64_t count, uint64_t* terms, int* side);
 
 /* Nijenhuis-Wilf prologue (gpu_exact_dense.cu:642-652): x0[j] = a[j][n-1] - rowsum_j/2,
  * p0 = prod x0.  Host-only helper, exported for the test harness. */

@@ -20,7 +20,7 @@ from ._lib import (KERNEL_DENSE, KERNEL_SKIPPER, KERNEL_SPARYSER, LEAF_FN, SCHED
                    SCHED_STATIC, SupApproxResult, SupError, SupOpts, SupReduceOpts, SupStats)
 
 __all__ = [
-    "perman", "perman_cpu", "perman_exact", "perman_exact_range", "perman_quad", "perman_quad_range", "perman_complex", "perman_complex_range", "perman_complex_batch", "perman_complex_submatrices", "read_mtx_complex", "partial", "perman_shard", "plan_info", "plan_key", "prepare", "read_matrix", "read_mtx", "sort_order",
+    "perman", "perman_cpu", "perman_exact", "perman_exact_range", "perman_quad", "perman_quad_range", "perman_complex", "perman_complex_range", "perman_complex_batch", "perman_complex_submatrices", "perman_complex_fock", "perman_complex_fock_plan", "read_mtx_complex", "partial", "perman_shard", "plan_info", "plan_key", "prepare", "read_matrix", "read_mtx", "sort_order",
     "skip_order", "compress", "decompose", "perman_reduced", "approx", "grid_graph", "ALGOS_APPROX",
     "nw_start", "device_count", "rccl_devices", "layout", "ShardCall", "SupError", "ALGOS_DENSE", "ALGOS_SPARSE",
     "gpu_perman64_xshared_coalescing_mshared",
@@ -352,6 +352,70 @@ def perman_complex_submatrices(U, rows, cols, gpu_num: int = 1, device_id: int =
                                                   out.ctypes.data, C.byref(st)), "perman_complex_submatrices")
     v = _batch_result(out, count)
     return (v, st.as_dict()) if return_stats else v
+
+
+def _fock_lists(rows, cols):
+    """rows / cols of shape [n] or [count, n] as contiguous int32 [count, n];
+    single: the lists had shape [n]."""
+    r, c = np.asarray(rows), np.asarray(cols)
+    single = r.ndim == 1
+    if single:
+        r, c = r[None, :], c[None, :] if c.ndim == 1 else c
+    if r.ndim != 2 or r.shape != c.shape:
+        raise ValueError(f"rows and cols must both have shape [n] or [count, n], got {np.shape(rows)} and "
+                         f"{np.shape(cols)}")
+    for name, ix in (("rows", r), ("cols", c)):
+        if ix.size and not np.issubdtype(ix.dtype, np.integer):
+            raise ValueError(f"{name} must be an integer array, got dtype {ix.dtype}")
+        if ix.size and (ix.min() < -2**31 or ix.max() >= 2**31):
+            raise ValueError(f"{name} holds an index outside the 32-bit range")
+    count, n = r.shape
+    if not 1 <= n <= 64:
+        raise ValueError(f"n = {n} outside [1, 64] (64-bit Gray index)")
+    r32 = np.ascontiguousarray(r, dtype=np.int32) if count else np.zeros(1, np.int32)
+    c32 = np.ascontiguousarray(c, dtype=np.int32) if count else np.zeros(1, np.int32)
+    return r32, c32, count, n, single
+
+
+def perman_complex_fock(U, rows, cols, gpu_num: int = 1, device_id: int = 0, cpu: bool = False, threads: int = 16,
+                        return_stats: bool = False):
+    """The permanents of n x n submatrices ``U[np.ix_(rows[k], cols[k])]`` of
+    one complex matrix U, as ``perman_complex_submatrices`` but collision
+    aware (sup_perman_complex_fock): equal indices on one side make equal
+    columns (or rows), and the sum then runs over the multiplicity vectors of
+    the side with fewer terms, T = prod (t'_k + 1) instead of 2^(n-1) (the
+    collision-aware walk walk_cplxf.hip, or (cpu=True) its host twin,
+    bit-identical).  Lists of shape [n] give one Python complex, of shape
+    [count, n] a complex128 array of shape [count].  The values equal
+    ``perman_complex_submatrices``' up to rounding, not bit for bit."""
+    u = np.ascontiguousarray(np.asarray(U, dtype=np.complex128))
+    if u.ndim != 2 or u.shape[0] < 1 or u.shape[1] < 1:
+        raise ValueError(f"expected a non-empty 2-d matrix U, got shape {u.shape}")
+    r32, c32, count, n, single = _fock_lists(rows, cols)
+    lib = _lib.load()
+    o = _opts(gpu_num=gpu_num, device_id=device_id, threads=threads)
+    out, st = np.zeros(2 * max(count, 1)), SupStats()
+    _lib.check(lib.sup_perman_complex_fock(u.ctypes.data, u.shape[0], u.shape[1], r32.ctypes.data, c32.ctypes.data,
+                                           n, count, C.byref(o), int(bool(cpu)), out.ctypes.data, C.byref(st)),
+               "perman_complex_fock")
+    v = _batch_result(out, count)
+    v = complex(v[0]) if single else v
+    return (v, st.as_dict()) if return_stats else v
+
+
+def perman_complex_fock_plan(rows, cols):
+    """What ``perman_complex_fock`` does with these lists
+    (sup_perman_complex_fock_plan, host only): (terms, side) — the terms T of
+    the sum and the side collapsed (0 columns, 1 rows); two ints for lists of
+    shape [n], two arrays of shape [count] for [count, n]."""
+    r32, c32, count, n, single = _fock_lists(rows, cols)
+    lib = _lib.load()
+    terms, side = np.zeros(max(count, 1), np.uint64), np.zeros(max(count, 1), np.int32)
+    _lib.check(lib.sup_perman_complex_fock_plan(r32.ctypes.data, c32.ctypes.data, n, count, terms.ctypes.data,
+                                                side.ctypes.data), "perman_complex_fock_plan")
+    if single:
+        return int(terms[0]), int(side[0])
+    return terms[:count].copy(), side[:count].copy()
 
 
 def partial(mat, start: int, end: int, kernel: str = "dense", gpu_num: int = 1, device_id: int = 0,

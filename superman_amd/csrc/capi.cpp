@@ -490,6 +490,40 @@ int sup_perman_complex_submatrices(const double* U, int R, int C, const int32_t*
   return complex_batch(in, n, count, o, on_cpu, out, st);
 }
 
+int sup_perman_complex_fock(const double* U, int R, int C, const int32_t* rows, const int32_t* cols, int n,
+                            uint64_t count, const sup_opts* o_in, int on_cpu, double* out, sup_stats* st) {
+  auto t0 = std::chrono::steady_clock::now();
+  if (!U || !rows || !cols || !out) {
+    set_error("sup_perman_complex_fock: null matrix, index list or output pointer");
+    return SUP_EINVAL;
+  }
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  CplxBatchIn in;
+  in.U = U, in.R = R, in.C = C, in.rows = rows, in.cols = cols;
+  FockInfo fi;
+  if (int rc = cplx_perman_fock(in, n, count, o, on_cpu != 0, out, &fi)) return rc;
+  if (st) {
+    std::memset(st, 0, sizeof(*st));
+    st->kernel_ms = fi.kernel_ms;
+    st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    st->gray_steps = count << (n - 1);  // nominal: the expanded matrices' walk
+    st->visited_steps = fi.terms;
+    st->devices_used = fi.devices;
+    st->grid = fi.grid;
+    st->walk_kind = (int)kWalkDense;
+    st->leaves = (int)std::min<uint64_t>(count, 0x7fffffffu);
+    st->est_ops_per_step = 6.0 * n;
+  }
+  return SUP_OK;
+}
+
+int sup_perman_complex_fock_plan(const int32_t* rows, const int32_t* cols, int n, uint64_t count, uint64_t* terms,
+                                 int* side) {
+  return cplx_fock_plan(rows, cols, n, count, terms, side);
+}
+
 int sup_perman_reduced_exact(const void* mat, sup_dtype t, int n, const sup_opts* o_in, int on_cpu,
                              const sup_reduce_opts* r_in, char* out, size_t out_len, sup_stats* st) {
   auto t0 = std::chrono::steady_clock::now();

@@ -121,6 +121,10 @@ struct DeviceCtx {
   size_t cbU_cap = 0;
   double* d_cbout = nullptr;
   size_t cbout_cap = 0;
+  // collision-aware complex walk (run_cplx_fock): a slab's step programs,
+  // digits, descriptors and the weight table, packed (16-byte units)
+  uint4* d_fock = nullptr;
+  size_t fock_cap = 0;
   uint64_t tables_uid = 0;  // Plan::uid whose cols / x0 / nblk / rowmask / jtab the device holds
   std::mutex mu;
   int occ[3][SUP_MAX_N + 1] = {};  // AOT kernels; segmented walk: jit_occupancy
@@ -1068,6 +1072,90 @@ int run_cplx_batch(int dev, int n, const Layout& lay, const CplxBatchIn& in, uin
   }
   if (kernel_ms) *kernel_ms = total_ms;
   return SUP_OK;
+}
+
+// Collision-aware complex walk (walk_cplxf.hip, cplx_fock.hip) of slab S on
+// device `dev`: U, the slab's index lists and its descriptor pools go up, then
+// prepare (tables and x(0) written on the device), the walk over the slab's
+// queue and the per-matrix fold run on the context's stream with no host work
+// between them, and one download brings 16 bytes per matrix into out.
+int run_cplx_fock(int dev, const FockSlab& S, const CplxBatchIn& in, double* out, double* kernel_ms, int* grid_out) {
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (grid_out) *grid_out = 0;
+  const uint64_t K = S.mats.size(), chunks = S.chunks.size();
+  if (K == 0) return SUP_OK;
+  if (S.n < 1 || S.n > SUP_MAX_N || chunks == 0 || chunks > 0x7fffffffull || !out || !in.U || !in.rows || !in.cols ||
+      in.R < 1 || in.C < 1) {
+    set_error("run_cplx_fock: bad request");
+    return SUP_EINVAL;
+  }
+  const std::vector<double>& wts = fock_weights();
+  // the packed pools, each starting on a 16-byte unit
+  auto units = [](size_t bytes) { return (bytes + 15) / 16; };
+  const size_t u_prog = 0, u_dig = u_prog + units(S.prog.size() * sizeof(FockStep));
+  const size_t u_mats = u_dig + units(S.dig.size() * sizeof(FockDigit));
+  const size_t u_chunks = u_mats + units(K * sizeof(FockMat));
+  const size_t u_wts = u_chunks + units(chunks * sizeof(FockChunk));
+  const size_t u_grp = u_wts + units(wts.size() * sizeof(double));
+  const size_t u_end = u_grp + units(S.grp.size() * sizeof(int32_t));
+  const size_t n = (size_t)S.n;
+  CtxGuard guard;
+  int rc = guard.open(dev, "device buffers");
+  if (rc) return rc;
+  DeviceCtx* c = guard.c;
+  int occ = 0;
+  SUP_HIP(cplx_fock_occupancy(S.n, &occ));
+  if ((rc = ensure(c->d_cbtab, c->cbtab_cap, (size_t)(S.tab_doubles + S.x0_doubles)))) return rc;
+  if ((rc = ensure(c->d_cbidx, c->cbidx_cap, (size_t)K * 2 * n))) return rc;
+  if ((rc = ensure(c->d_cbU, c->cbU_cap, (size_t)2 * in.R * in.C))) return rc;
+  if ((rc = ensure(c->d_chunk, c->chunk_cap, (size_t)(2 * chunks)))) return rc;
+  if ((rc = ensure(c->d_cbout, c->cbout_cap, (size_t)K * 2))) return rc;
+  if ((rc = ensure(c->d_fock, c->fock_cap, u_end))) return rc;
+  hipStream_t s = c->stream;
+  c->tables_uid = 0;  // the walk leaves head 0 nonzero
+  c->head_zero[0] = false;
+  double* d_tabs = c->d_cbtab;
+  double* d_x0s = c->d_cbtab + S.tab_doubles;
+  int32_t* d_rows = c->d_cbidx;
+  int32_t* d_cols = c->d_cbidx + (size_t)K * n;
+  auto up = [&](void* dst, const void* src, size_t bytes) {
+    return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+  };
+  SUP_HIP(up(c->d_cbU, in.U, (size_t)2 * in.R * in.C * sizeof(double)));
+  SUP_HIP(up(d_rows, in.rows + S.first * n, (size_t)K * n * sizeof(int32_t)));
+  SUP_HIP(up(d_cols, in.cols + S.first * n, (size_t)K * n * sizeof(int32_t)));
+  SUP_HIP(up(c->d_fock + u_grp, S.grp.data(), S.grp.size() * sizeof(int32_t)));
+  SUP_HIP(up(c->d_fock + u_prog, S.prog.data(), S.prog.size() * sizeof(FockStep)));
+  SUP_HIP(up(c->d_fock + u_dig, S.dig.data(), S.dig.size() * sizeof(FockDigit)));
+  SUP_HIP(up(c->d_fock + u_mats, S.mats.data(), K * sizeof(FockMat)));
+  SUP_HIP(up(c->d_fock + u_chunks, S.chunks.data(), chunks * sizeof(FockChunk)));
+  SUP_HIP(up(c->d_fock + u_wts, wts.data(), wts.size() * sizeof(double)));
+  SUP_HIP(hipMemsetAsync(c->d_counter, 0, sizeof(unsigned), s));
+  const uint64_t resident = (uint64_t)c->cus * (uint64_t)std::max(occ, 1);
+  const char* fg = std::getenv("SUP_WALK_GROUP");  // tests, read per call: chunks per ticket (the bits do not change)
+  const LaunchGeom geo = walk_geometry(chunks, resident, kWavesPerBlock, false, fg ? std::max(1, std::atoi(fg)) : 0);
+  FockParams p{};
+  p.tabs = d_tabs;
+  p.x0s = d_x0s;
+  p.prog = reinterpret_cast<const FockStep*>(c->d_fock + u_prog);
+  p.dig = reinterpret_cast<const FockDigit*>(c->d_fock + u_dig);
+  p.mats = reinterpret_cast<const FockMat*>(c->d_fock + u_mats);
+  p.chunks = reinterpret_cast<const FockChunk*>(c->d_fock + u_chunks);
+  p.wts = reinterpret_cast<const double*>(c->d_fock + u_wts);
+  p.chunk_count = chunks;
+  p.chunk_out = c->d_chunk;
+  p.counter = c->d_counter;
+  p.group = geo.group;
+  SUP_HIP(hipEventRecord(c->ev0, s));
+  SUP_ON_DEVICE(c->dev, "collision-aware complex walk launch");
+  SUP_HIP(launch_cplx_fock_prepare(c->d_cbU, in.C, d_rows, d_cols, reinterpret_cast<const int32_t*>(c->d_fock + u_grp),
+                                   p.mats, S.n, K, d_tabs, d_x0s, s));
+  SUP_HIP(launch_cplx_fock(S.n, p, (int)geo.grid, s));
+  SUP_HIP(launch_cplx_fock_fold(c->d_chunk, p.mats, K, c->d_cbout, s));
+  SUP_HIP(hipEventRecord(c->ev1, s));
+  SUP_HIP(hipMemcpyAsync(out, c->d_cbout, (size_t)K * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (grid_out) *grid_out = (int)geo.grid;
+  return timed_sync(c, kernel_ms);
 }
 
 }  // namespace sup

@@ -523,4 +523,41 @@ int run_cplx_batch(int dev, int n, const Layout& lay, const CplxBatchIn& in, uin
 int cplx_perman_batch(const CplxBatchIn& in, int n, uint64_t count, const sup_opts& o, bool on_cpu, double* out,
                       CplxInfo* info);
 
+// ---- collision-aware complex permanents (cplx_fock.cpp; walk_cplxf.hip, cplx_fock.hip) ----
+// A slab of K matrices of order n as the walk reads it (cplx_fock.hpp): the
+// pools and descriptors, built on the host by cplx_fock.cpp.
+struct FockSlab {
+  int n = 0;
+  uint64_t first = 0;                    // the slab's first matrix: its lists start at rows + first n
+  uint64_t tab_doubles = 0, x0_doubles = 0;  // sizes of tabs and x0s
+  std::vector<double> tabs, x0s;         // filled for the host twin only: the device writes its own
+  std::vector<FockStep> prog;
+  std::vector<FockDigit> dig;
+  std::vector<int32_t> grp;
+  std::vector<FockMat> mats;
+  std::vector<FockChunk> chunks;
+};
+// (-1)^v C(t, v), t < 64, row t at t (t + 1) / 2 (FockParams::wts).
+const std::vector<double>& fock_weights();
+// Prepares (tables and x(0) from in.U and the slab's lists), walks and folds
+// slab S on device `dev`: out[2k], out[2k + 1] = the permanent of its matrix
+// k, bit-identical to the host twin.  *kernel_ms: prepare + walk + fold kernel
+// time; *grid: blocks of the walk launch.
+int run_cplx_fock(int dev, const FockSlab& S, const CplxBatchIn& in, double* out, double* kernel_ms,
+                  int* grid = nullptr);
+struct FockInfo {
+  double kernel_ms = 0.0;
+  int devices = 0, grid = 0;
+  uint64_t terms = 0;  // sum over the matrices of T
+};
+// out[2k], out[2k + 1] = the permanent of the submatrix k of in.U picked by
+// in.rows / in.cols (sup_perman_complex_fock): the sum over the multiplicity
+// vectors of the side with fewer terms.  Checks as cplx_perman_batch's
+// submatrix form, before any work.
+int cplx_perman_fock(const CplxBatchIn& in, int n, uint64_t count, const sup_opts& o, bool on_cpu, double* out,
+                     FockInfo* info);
+// Per matrix the terms T of that sum and the side collapsed (0 columns,
+// 1 rows); either output may be null.  Host only.
+int cplx_fock_plan(const int32_t* rows, const int32_t* cols, int n, uint64_t count, uint64_t* terms, int* side);
+
 }  // namespace sup

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "cplx_fock.hpp"
 #include "walk_batch.hpp"
 #include "walk_params.hpp"
 
@@ -84,6 +85,14 @@ SUP_DECL_CPLX(49)
 SUP_DECL_CPLXB(1)
 SUP_DECL_CPLXB(17)
 #undef SUP_DECL_CPLXB
+#define SUP_DECL_CPLXF(LO)                                                              \
+  hipError_t launch_cplxf_##LO(int n, const FockParams& p, int grid, hipStream_t s);   \
+  hipError_t occupancy_cplxf_##LO(int n, int* blocks_per_cu);
+SUP_DECL_CPLXF(1)
+SUP_DECL_CPLXF(17)
+SUP_DECL_CPLXF(33)
+SUP_DECL_CPLXF(49)
+#undef SUP_DECL_CPLXF
 #define SUP_DECL_LDS(LO)                                                                  \
   hipError_t launch_lds_##LO(int n, const WalkParams& p, int grid, hipStream_t s);        \
   hipError_t occupancy_lds_##LO(int n, int m, int* blocks_per_cu);
@@ -154,6 +163,20 @@ hipError_t launch_cplx_batch_prepare(const CplxBatchSrc& src, int n, uint64_t K,
 // out[2k], out[2k + 1] = (4(n&1) - 2) x the pairwise tree over matrix k's
 // 2^hbits (re, im) partials at parts + 2 (k << hbits).
 hipError_t launch_cplx_batch_fold(const double* parts, int n, int hbits, uint64_t K, double* out, hipStream_t s);
+
+// Collision-aware complex walk (walk_cplxf.hip, n <= 64): the wave-chunks of a
+// slab of matrices in one queue, described by FockParams (cplx_fock.hpp).
+hipError_t launch_cplx_fock(int n, const FockParams& p, int grid, hipStream_t s);
+hipError_t cplx_fock_occupancy(int n, int* blocks_per_cu);
+// The signed column tables and x(0) of the K matrices of a slab, written from
+// U (C its row length) and the slab's index lists (K x n each) as
+// cplx_fock.cpp's fock_append writes them on the host: mats[k] names matrix
+// k's offsets, side and groups (grp: index value, multiplicity pairs).
+hipError_t launch_cplx_fock_prepare(const double* U, int C, const int32_t* rows, const int32_t* cols, const int32_t* grp,
+                                    const FockMat* mats, int n, uint64_t K, double* tabs, double* x0s, hipStream_t s);
+// out[2k], out[2k + 1] = 2 x fock_fold over matrix k's (re, im) partials at
+// parts + 2 mats[k].chunk0 (cplx_fock.hip).
+hipError_t launch_cplx_fock_fold(const double* parts, const FockMat* mats, uint64_t K, double* out, hipStream_t s);
 
 // Fixed-order pairwise reduction of `count` doubles into *out (64-way passes,
 // zero padded; mirrored by oracle/oracle.c orc_pairwise_reduce).  `scratch`

@@ -5,11 +5,14 @@ For every N of the chosen kernel it prints one line in the columns of
 profiles/complex/walk_cplx_resources.log: hipcc's
 -Rpass-analysis=kernel-resource-usage figures, then a scan of the -S output:
 the walk loop (the innermost loop with the most fp64 VALU instructions: one odd
-+ one even Gray step, 2(6N - 2) of them) with its scratch instructions, AGPR
++ one even Gray step, 2(6N - 2) of them; the collision-aware walk's loop is one
+step, 6N of them: 2N column adds, 4(N - 1) for the product, 4 for acc += w term)
+with its scratch instructions, AGPR
 moves, v_mov and readlane / writelane, and the scratch instructions of the
 whole kernel.
 
   python tools/probes/cplx_resources.py batch > profiles/complex_batch/walk_cplx_batch_resources.log
+  python tools/probes/cplx_resources.py fock > profiles/complex_fock/walk_cplx_fock_resources.log
   python tools/probes/cplx_resources.py single --ranges 1_16 17_32   # walk_cplx<N>, to diff against its log
 """
 import argparse
@@ -21,7 +24,12 @@ import tempfile
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "superman_amd", "csrc")
 KERNELS = {"batch": ("walk_cplxb.hip", "walk_cplx_batch", ["1_16", "17_32"]),
-           "single": ("walk_cplx.hip", "walk_cplx", ["1_16", "17_32", "33_48", "49_64"])}
+           "single": ("walk_cplx.hip", "walk_cplx", ["1_16", "17_32", "33_48", "49_64"]),
+           "fock": ("walk_cplxf.hip", "walk_cplx_fock", ["1_16", "17_32", "33_48", "49_64"])}
+# fp64 VALU instructions of the walk loop at order n, and how the logs name that count
+LOOP = {"fock": (lambda n: 6 * n, "6N", "one step")}
+loop_f64, loop_name, loop_what = LOOP.get(sys.argv[1] if len(sys.argv) > 1 else "", (
+    lambda n: 2 * (6 * n - 2), "2(6N-2)", "one odd + one even Gray step"))
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 
 ap = argparse.ArgumentParser()
@@ -79,12 +87,21 @@ for r in ranges:
                    f"{d['SGPRs Spill']} {d['ScratchSize [bytes/lane]']} | {c[0]} {c[1]} {c[2]} {c[3]} {c[4]} | {c[5]}")
 
 print(f"# {kname}<N>, gfx950, hipcc -O3 -ffp-contract=off: -Rpass-analysis=kernel-resource-usage per N, and the walk loop")
-print("# (the innermost loop holding 2(6N-2) fp64 VALU instructions: one odd + one even Gray step) scanned in the -S output.")
+print(f"# (the innermost loop holding {loop_name} fp64 VALU instructions: {loop_what}) scanned in the -S output.")
 print("# N waves/SIMD VGPRs AGPRs SGPRs spilled_VGPRs spilled_SGPRs scratch_bytes | loop: f64_insts scratch_insts "
       "accvgpr_moves v_mov readlane/writelane | kernel_scratch_insts")
 for n in sorted(rows):
     print(rows[n])
-bad = [n for n in sorted(rows) if not re.search(rf"\| {2 * (6 * n - 2)} 0 ", rows[n]) or rows[n].split()[5] != "0"
+bad = [n for n in sorted(rows) if not re.search(rf"\| {loop_f64(n)} 0 ", rows[n]) or rows[n].split()[5] != "0"
        or rows[n].split()[7] != "0"]
-print(f"# condition (0 spilled VGPRs, 0 scratch bytes, loop = 2(6N-2) fp64 instructions, no scratch in it): "
-      f"{'holds at every N' if not bad else 'FAILS at N = ' + ', '.join(map(str, bad))}")
+if args.kernel == "fock":
+    # the collision-aware walk's condition is on the walk loop; spills outside it (the chunk start) are listed
+    bad = [n for n in sorted(rows) if not re.search(rf"\| {loop_f64(n)} 0 ", rows[n])]
+    out = [n for n in sorted(rows) if rows[n].split()[5] != "0"]
+    print(f"# condition (walk loop = {loop_name} fp64 instructions, no scratch instruction in it): "
+          f"{'holds at every N' if not bad else 'FAILS at N = ' + ', '.join(map(str, bad))}")
+    print(f"# VGPRs spilled outside the walk loop (chunk start; to scratch where scratch_bytes > 0, else to AGPRs): "
+          f"{'none' if not out else 'N = ' + ', '.join(map(str, out))}")
+else:
+    print(f"# condition (0 spilled VGPRs, 0 scratch bytes, loop = {loop_name} fp64 instructions, no scratch in it): "
+          f"{'holds at every N' if not bad else 'FAILS at N = ' + ', '.join(map(str, bad))}")

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SUP_ABI_VERSION 14  /* 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
+#define SUP_ABI_VERSION 15  /* 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SUP_OK            0
@@ -441,6 +441,76 @@ int sup_perman_complex_fock(const double* U, int R, int C, const int32_t* rows,
  * [1, 64]: SUP_EINVAL.  Indices are only compared, not range-checked. */
 int sup_perman_complex_fock_plan(const int32_t* rows, const int32_t* cols, int n,
                                  uint64_t count, uint64_t* terms, int* side);
+
+/* One-walk permanent minors (ABI 15).  B is n x (n-1) complex; "minor j" is B
+ * without row j, (n-1) x (n-1).  The exact boson sampler (sup_boson_sample)
+ * needs, per stage, the permanents of all n minors of one matrix, and they are
+ * the gradient of a permanent with respect to a row.  n calls of
+ * sup_perman_complex walk the same 2^(n-3) Gray states with the same row sums
+ * n times; here all n fall out of one walk: with q = n - 1, the
+ * layout and enumeration of order q (o->walk_log2 honoured; engine bit e =
+ * column e, column q - 1 held) and the Nijenhuis-Wilf vector over all n rows,
+ *   x_i(S) = b_i,q-1 - 1/2 sum_c b_ic + sum_{e in S} b_ie
+ *   per(minor j) = (4(q&1) - 2) sum_S (-1)^|S| prod_{i != j} x_i(S),
+ * every state's n products formed from prefix and suffix products (cxm.hpp):
+ * 16n - 24 fp64 operations per Gray step for n results, against n (6(n-1) - 2).
+ * count x n minors: matrix k is B[j][c] = U[rows[k*n + j]][cols[k*(n-1) + c]]
+ * (n rows, n-1 columns, indices may repeat; never materialised on the device);
+ * out[2*(k*n + j)], [.. + 1] = per(B without row j).
+ * n = 1: the one minor is the empty matrix, 1 + 0i, no device work (cols may
+ * be NULL only here).  n <= 32: the one walk (walk_cplxm.hip).  Result (k, j)
+ * is then a function of (gathered B, o->walk_log2) only: bit-identical on the
+ * GPU, for any device count and slab size, and on any number of host threads
+ * (on_cpu = 1); it does NOT have sup_perman_complex's bits on the materialised
+ * minor (the product order differs).  n in 33..64: every minor materialised
+ * and run through sup_perman_complex's walk, on the device or the host as
+ * on_cpu says, with that entry's bits.
+ * Everything else as sup_perman_complex_submatrices: the same index checks and
+ * messages (k, the position and the value) before any device work, count == 0
+ * is SUP_OK, a null pointer or o->walk_log2 outside [0, 31] SUP_EINVAL, no
+ * device with on_cpu = 0 SUP_ENODEV (no silent CPU fallback), NaN stays inside
+ * its own matrix, o->gpu_num devices take contiguous ranges of matrices, slabs
+ * of 256 MiB (three launches and one download each) with the environment
+ * variable SUP_CPLX_MINORS_SLAB=<matrices> as the test override.
+ * st: as the batch entry's with leaves = count n, gray_steps = count 2^(n-2),
+ * est_ops_per_step = 16n - 24. */
+int sup_perman_complex_minors(const double* U, int R, int C, const int32_t* rows, const int32_t* cols,
+                              int n, uint64_t count, const sup_opts* o, int on_cpu, double* out, sup_stats* st);
+/* One raw n x (n-1) matrix (row-major interleaved), wave-chunks [c0, c1) of the
+ * order-(n-1) plan, per output the pairwise tree over c - c0, NOT scaled by
+ * 4((n-1)&1) - 2: out = 2n doubles.  Aligned power-of-two ranges folded
+ * pairwise in order, then scaled, reproduce sup_perman_complex_minors' bits.
+ * n outside [2, 32]: SUP_EUNSUPPORTED.  Errors and st otherwise as
+ * sup_perman_complex_range (est_ops_per_step = 16n - 24). */
+int sup_perman_complex_minors_range(const double* mat, int n, uint64_t c0, uint64_t c1, const sup_opts* o,
+                                    int on_cpu, double* out, sup_stats* st);
+/* nsamples exact boson-sampling outcomes (Clifford & Clifford 2018, algorithm
+ * A): n photons enter the M x M unitary U (row-major interleaved) in the
+ * distinct modes inputs[0..n); out = nsamples x n output modes, ascending per
+ * sample (a mode repeats where photons collide).  Stage k = 1..n is one
+ * sup_perman_complex_minors call of order parameter k over all samples (on
+ * U^T, rows = the first k of the sample's permuted inputs alpha, cols = its
+ * k - 1 modes drawn so far), then on o->threads host threads the weights
+ *   w_i = |sum_l U[i][alpha_l] minor_l|^2, i < M,
+ * and the draw, for both on_cpu values: the device and the host twin draw
+ * identical samples, and sample s depends on (U, inputs, seed, s) only, not on
+ * nsamples, threads, devices or slab size.
+ * Randomness: Philox4x32-10 with counter (s, step) keyed by seed; w64 = word 0
+ * | word 1 << 32 of that draw.  Shuffle: alpha starts as inputs; for t = 0 ..
+ * n-2, i = n-1-t: swap(alpha[i], alpha[floor(w64(step t) (i+1) / 2^64)]).
+ * Stage k: u = (w64(step 64 + k) >> 11) 2^-53; r_k = the first i whose running
+ * sum of w (ascending) exceeds u sum(w); an i with w_i = 0 is never chosen.
+ * n in [1, 32] (larger: SUP_EUNSUPPORTED); M >= 1 and inputs in [0, M), else
+ * SUP_EINVAL; a repeated input mode is SUP_EINVAL (the message names the
+ * position): the algorithm's marginals need orthonormal columns; likewise the
+ * n used columns A of U must satisfy |A^dagger A - I| <= 1e-8 entrywise.
+ * nsamples == 0: SUP_OK.  No device with on_cpu = 0: SUP_ENODEV.
+ * st: kernel_ms (summed over the stages), wall_ms, leaves = nsamples,
+ * gray_steps = nsamples sum_k 2^(k-2), devices_used, est_ops_per_step =
+ * 16n - 24, partials[0] / [1] = wall ms in the minors calls / in the host pmf
+ * stage. */
+int sup_boson_sample(const double* U, int M, const int32_t* inputs, int n, uint64_t nsamples, uint64_t seed,
+                     const sup_opts* o, int on_cpu, int32_t* out /* nsamples x n, ascending modes */, sup_stats* st);
 
 /* Nijenhuis-Wilf prologue (gpu_exact_dense.cu:642-652): x0[j] = a[j][n-1] - rowsum_j/2,
  * p0 = prod x0.  Host-only helper, exported for the test harness. */

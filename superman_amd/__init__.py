@@ -20,7 +20,7 @@ from ._lib import (KERNEL_DENSE, KERNEL_SKIPPER, KERNEL_SPARYSER, LEAF_FN, SCHED
                    SCHED_STATIC, SupApproxResult, SupError, SupOpts, SupReduceOpts, SupStats)
 
 __all__ = [
-    "perman", "perman_cpu", "perman_exact", "perman_exact_range", "perman_quad", "perman_quad_range", "perman_complex", "perman_complex_range", "perman_complex_batch", "perman_complex_submatrices", "perman_complex_fock", "perman_complex_fock_plan", "read_mtx_complex", "partial", "perman_shard", "plan_info", "plan_key", "prepare", "read_matrix", "read_mtx", "sort_order",
+    "perman", "perman_cpu", "perman_exact", "perman_exact_range", "perman_quad", "perman_quad_range", "perman_complex", "perman_complex_range", "perman_complex_batch", "perman_complex_submatrices", "perman_complex_fock", "perman_complex_fock_plan", "perman_complex_minors", "perman_complex_minors_submatrices", "perman_complex_minors_range", "boson_sample", "read_mtx_complex", "partial", "perman_shard", "plan_info", "plan_key", "prepare", "read_matrix", "read_mtx", "sort_order",
     "skip_order", "compress", "decompose", "perman_reduced", "approx", "grid_graph", "ALGOS_APPROX",
     "nw_start", "device_count", "rccl_devices", "layout", "ShardCall", "SupError", "ALGOS_DENSE", "ALGOS_SPARSE",
     "gpu_perman64_xshared_coalescing_mshared",
@@ -352,6 +352,129 @@ def perman_complex_submatrices(U, rows, cols, gpu_num: int = 1, device_id: int =
                                                   out.ctypes.data, C.byref(st)), "perman_complex_submatrices")
     v = _batch_result(out, count)
     return (v, st.as_dict()) if return_stats else v
+
+
+def _index_array(name: str, ix, width: int) -> np.ndarray:
+    ix = np.asarray(ix)
+    if ix.ndim != 2 or ix.shape[1] != width:
+        raise ValueError(f"{name} must have shape [count, {width}], got {ix.shape}")
+    if ix.size and not np.issubdtype(ix.dtype, np.integer):
+        raise ValueError(f"{name} must be an integer array, got dtype {ix.dtype}")
+    if ix.size and (ix.min() < -2**31 or ix.max() >= 2**31):
+        raise ValueError(f"{name} holds an index outside the 32-bit range")
+    return np.ascontiguousarray(ix, dtype=np.int32) if ix.size else np.zeros(1, np.int32)
+
+
+def perman_complex_minors_submatrices(U, rows, cols, gpu_num: int = 1, device_id: int = 0, cpu: bool = False,
+                                      threads: int = 16, walk_log2: int = 0, return_stats: bool = False):
+    """The permanents of all n minors of ``count`` n x (n-1) submatrices of one
+    complex matrix U (sup_perman_complex_minors): ``rows`` has shape [count, n],
+    ``cols`` shape [count, n-1], matrix k is ``B = U[np.ix_(rows[k], cols[k])]``
+    (indices may repeat) and result [k, j] the permanent of B without row j —
+    all n from one Gray walk per matrix (walk_cplxm.hip for n <= 32).
+    np.ndarray complex128 of shape [count, n]; a function of (B, walk_log2)
+    only: bit-identical on the GPU, on any device count and (cpu=True) on host
+    threads.  n = 1 gives ones (the empty minor)."""
+    u = np.ascontiguousarray(np.asarray(U, dtype=np.complex128))
+    if u.ndim != 2 or u.shape[0] < 1 or u.shape[1] < 1:
+        raise ValueError(f"expected a non-empty 2-d matrix U, got shape {u.shape}")
+    r = np.asarray(rows)
+    if r.ndim != 2:
+        raise ValueError(f"rows must have shape [count, n], got {r.shape}")
+    count, n = r.shape
+    if not 1 <= n <= 64:
+        raise ValueError(f"n = {n} outside [1, 64] (64-bit Gray index)")
+    c = np.asarray(cols)
+    if c.shape != (count, n - 1):
+        raise ValueError(f"cols must have shape [count, n - 1] = {(count, n - 1)}, got {c.shape}")
+    r32 = _index_array("rows", r, n)
+    c32 = _index_array("cols", c.reshape(count, n - 1), n - 1)
+    lib = _lib.load()
+    o = _opts(gpu_num=gpu_num, device_id=device_id, threads=threads, walk_log2=walk_log2)
+    out, st = np.zeros(2 * max(count * n, 1)), SupStats()
+    _lib.check(lib.sup_perman_complex_minors(u.ctypes.data, u.shape[0], u.shape[1], r32.ctypes.data, c32.ctypes.data,
+                                             n, count, C.byref(o), int(bool(cpu)), out.ctypes.data, C.byref(st)),
+               "perman_complex_minors_submatrices")
+    v = _batch_result(out, count * n).reshape(count, n)
+    return (v, st.as_dict()) if return_stats else v
+
+
+def _minors_mat(B) -> tuple[np.ndarray, int]:
+    b = np.ascontiguousarray(np.asarray(B, dtype=np.complex128))
+    if b.ndim != 2 or b.shape[0] < 1 or b.shape[1] != b.shape[0] - 1:
+        raise ValueError(f"expected an n x (n-1) matrix, got shape {b.shape}")
+    return b, b.shape[0]
+
+
+def perman_complex_minors(B, gpu_num: int = 1, device_id: int = 0, cpu: bool = False, threads: int = 16,
+                          walk_log2: int = 0, return_stats: bool = False):
+    """The permanents of the n minors of one n x (n-1) complex matrix B: value
+    j is the permanent of B without row j (the gradient of the permanent of
+    [B | v] with respect to v).  np.ndarray complex128 of shape [n]; goes
+    through ``perman_complex_minors_submatrices`` with identity lists."""
+    b, n = _minors_mat(B)
+    if not 1 <= n <= 64:
+        raise ValueError(f"n = {n} outside [1, 64] (64-bit Gray index)")
+    u = b if n > 1 else np.zeros((1, 1), np.complex128)
+    rows = np.arange(n, dtype=np.int32)[None, :]
+    cols = np.arange(n - 1, dtype=np.int32)[None, :]
+    res = perman_complex_minors_submatrices(u, rows, cols, gpu_num=gpu_num, device_id=device_id, cpu=cpu,
+                                            threads=threads, walk_log2=walk_log2, return_stats=return_stats)
+    return (res[0][0], res[1]) if return_stats else res[0]
+
+
+def perman_complex_minors_range(B, c0: int, c1: int, cpu: bool = False, threads: int = 16, device_id: int = 0,
+                                walk_log2: int = 0, return_stats: bool = False):
+    """Per minor of the n x (n-1) matrix B (n in [2, 32]) the part of its sum
+    from wave-chunks [c0, c1) of the order-(n-1) plan, folded pairwise over
+    c - c0 and not scaled by 4((n-1)&1)-2: aligned power-of-two ranges folded
+    pairwise in order, then scaled, reproduce perman_complex_minors' bits.
+    np.ndarray complex128 of shape [n].  One device, or (cpu=True) host threads."""
+    b, n = _minors_mat(B)
+    lib = _lib.load()
+    o = _opts(device_id=device_id, threads=threads, walk_log2=walk_log2)
+    out, st = np.zeros(2 * n), SupStats()
+    src = b if b.size else np.zeros(2)
+    _lib.check(lib.sup_perman_complex_minors_range(src.ctypes.data, n, int(c0), int(c1), C.byref(o), int(bool(cpu)),
+                                                   out.ctypes.data, C.byref(st)), "perman_complex_minors_range")
+    v = _batch_result(out, n)
+    return (v, st.as_dict()) if return_stats else v
+
+
+def boson_sample(U, inputs, nsamples: int, seed: int = 0, gpu_num: int = 1, device_id: int = 0, cpu: bool = False,
+                 threads: int = 16, walk_log2: int = 0, return_stats: bool = False):
+    """``nsamples`` exact boson-sampling outcomes (Clifford & Clifford 2018,
+    algorithm A; sup_boson_sample): n = len(inputs) photons enter the M x M
+    unitary U in the distinct modes ``inputs``.  np.ndarray int32 of shape
+    [nsamples, n]: each row the output modes, ascending (a mode repeats where
+    photons collide).  Sample s depends on (U, inputs, seed, s) only — the
+    GPU and (cpu=True) the host twin draw identical samples."""
+    u = np.ascontiguousarray(np.asarray(U, dtype=np.complex128))
+    if u.ndim != 2 or u.shape[0] != u.shape[1] or u.shape[0] < 1:
+        raise ValueError(f"expected a square matrix U, got shape {u.shape}")
+    ins = np.asarray(inputs)
+    if ins.ndim != 1 or ins.size < 1:
+        raise ValueError(f"inputs must be a non-empty 1-d list of modes, got shape {ins.shape}")
+    if not np.issubdtype(ins.dtype, np.integer):
+        raise ValueError(f"inputs must be integers, got dtype {ins.dtype}")
+    if ins.min() < -2**31 or ins.max() >= 2**31:
+        raise ValueError("inputs holds a mode outside the 32-bit range")
+    i32 = np.ascontiguousarray(ins, dtype=np.int32)
+    nsamples, n = int(nsamples), int(i32.size)
+    if nsamples < 0:
+        raise ValueError("nsamples must be >= 0")
+    lib = _lib.load()
+    o = _opts(gpu_num=gpu_num, device_id=device_id, threads=threads, walk_log2=walk_log2)
+    out, st = np.zeros((max(nsamples, 1), n), np.int32), SupStats()
+    _lib.check(lib.sup_boson_sample(u.ctypes.data, u.shape[0], i32.ctypes.data, n, nsamples,
+                                    int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(o), int(bool(cpu)), out.ctypes.data,
+                                    C.byref(st)), "boson_sample")
+    v = out[:nsamples].copy()
+    if not return_stats:
+        return v
+    d = st.as_dict()
+    d["minors_ms"], d["pmf_ms"] = float(st.partials[0]), float(st.partials[1])
+    return v, d
 
 
 def _fock_lists(rows, cols):

@@ -524,6 +524,73 @@ int sup_perman_complex_fock_plan(const int32_t* rows, const int32_t* cols, int n
   return cplx_fock_plan(rows, cols, n, count, terms, side);
 }
 
+// sup_stats of a minors call: the batch entry's, with the one-walk step cost.
+static void fill_minors_stats(sup_stats* st, const CplxInfo& ci, int n, uint64_t outputs, uint64_t steps,
+                              double wall_ms) {
+  fill_cplx_stats(st, ci, n, steps, wall_ms);
+  if (!st) return;
+  st->leaves = (int)std::min<uint64_t>(outputs, 0x7fffffffu);
+  st->est_ops_per_step = n <= 32 ? std::max(16.0 * n - 24.0, 0.0) : 6.0 * (n - 1);
+}
+
+int sup_perman_complex_minors(const double* U, int R, int C, const int32_t* rows, const int32_t* cols, int n,
+                              uint64_t count, const sup_opts* o_in, int on_cpu, double* out, sup_stats* st) {
+  auto t0 = std::chrono::steady_clock::now();
+  if (!U || !rows || (!cols && n != 1) || !out) {
+    set_error("sup_perman_complex_minors: null matrix, index list or output pointer");
+    return SUP_EINVAL;
+  }
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  CplxBatchIn in;
+  in.U = U, in.R = R, in.C = C, in.rows = rows, in.cols = cols;
+  CplxInfo ci;
+  if (int rc = cplx_minors(in, n, count, o, on_cpu != 0, out, &ci)) return rc;
+  const double wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  // n <= 32: one walk of 2^(q-1) states per matrix; above, n walks of order q
+  const uint64_t per = n <= 1 ? 0 : n <= 32 ? 1ull << (n - 2) : (uint64_t)n << (n - 2);
+  fill_minors_stats(st, ci, n, count * (uint64_t)n, count * per, wall);
+  return SUP_OK;
+}
+
+int sup_perman_complex_minors_range(const double* mat, int n, uint64_t c0, uint64_t c1, const sup_opts* o_in,
+                                    int on_cpu, double* out, sup_stats* st) {
+  auto t0 = std::chrono::steady_clock::now();
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  CplxInfo ci;
+  if (int rc = cplx_minors_range(mat, n, c0, c1, o, on_cpu != 0, out, &ci)) return rc;
+  const double wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  fill_minors_stats(st, ci, n, 1, (c1 - c0) << (ci.lay.L + ci.lay.m), wall);
+  return SUP_OK;
+}
+
+int sup_boson_sample(const double* U, int M, const int32_t* inputs, int n, uint64_t nsamples, uint64_t seed,
+                     const sup_opts* o_in, int on_cpu, int32_t* out, sup_stats* st) {
+  auto t0 = std::chrono::steady_clock::now();
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  BosonInfo bi;
+  if (int rc = boson_sample(U, M, inputs, n, nsamples, seed, o, on_cpu != 0, out, &bi)) return rc;
+  if (st) {
+    std::memset(st, 0, sizeof(*st));
+    st->kernel_ms = bi.kernel_ms;
+    st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    st->gray_steps = bi.steps;
+    st->visited_steps = bi.steps;
+    st->devices_used = bi.devices;
+    st->walk_kind = (int)kWalkDense;
+    st->leaves = (int)std::min<uint64_t>(nsamples, 0x7fffffffu);
+    st->est_ops_per_step = std::max(16.0 * n - 24.0, 0.0);
+    st->partials[0] = bi.minors_ms;  // wall time inside the minors calls
+    st->partials[1] = bi.pmf_ms;     // wall time of the host pmf and draw stage
+  }
+  return SUP_OK;
+}
+
 int sup_perman_reduced_exact(const void* mat, sup_dtype t, int n, const sup_opts* o_in, int on_cpu,
                              const sup_reduce_opts* r_in, char* out, size_t out_len, sup_stats* st) {
   auto t0 = std::chrono::steady_clock::now();

@@ -1074,6 +1074,113 @@ int run_cplx_batch(int dev, int n, const Layout& lay, const CplxBatchIn& in, uin
   return SUP_OK;
 }
 
+// One-walk minors (walk_cplxm.hip, cplx_minors.hip) of matrices [k0, k1) of
+// `in` (n rows, n - 1 columns, 2 <= n <= 32; lay: the layout of order n - 1)
+// on device `dev`, in slabs of K matrices as run_cplx_batch's: U goes up once
+// per call, per slab its index lists, then prepare, walk and fold
+// (cplx_batch_fold over K n outputs of order n - 1) on the context's stream and
+// one download of 16 K n bytes into out[2 (k - k0) n].  c0 < c1 (one matrix,
+// k1 = k0 + 1): the range form, no fold, the partials [j][c - c0] come down.
+// The buffers are the batched walk's (same context lock).
+static int run_cplx_minors_impl(int dev, int n, const Layout& lay, const CplxBatchIn& in, uint64_t k0, uint64_t k1,
+                                uint64_t c0, uint64_t c1, double* out, double* kernel_ms, int* grid_out) {
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (grid_out) *grid_out = 0;
+  if (k1 <= k0) return SUP_OK;
+  const bool range = c1 > c0;
+  const int q = n - 1;
+  if (n < 2 || n > 32 || lay.L + lay.m + lay.h != q - 1 || lay.h > 24 || !(in.U && in.rows && in.cols) || !out ||
+      (range && (k1 != k0 + 1 || c1 > lay.chunks()))) {
+    set_error("run_cplx_minors: bad request");
+    return SUP_EINVAL;
+  }
+  const size_t NP = (size_t)pad8(n), plane = (size_t)2 * std::max(q - 1, 1) * NP;
+  const size_t tab = 2 * plane, per_chunks = range ? (size_t)(c1 - c0) : (size_t)1 << lay.h;
+  const size_t per_bytes = (tab + 2 * NP + (2 * per_chunks + 2) * n + (size_t)n) * sizeof(double);
+  uint64_t K = std::max<uint64_t>(1, kCplxBatchCapBytes / per_bytes);
+  if (const char* e = std::getenv("SUP_CPLX_MINORS_SLAB")) {
+    const long long v = std::atoll(e);
+    if (v > 0) K = (uint64_t)v;
+  }
+  K = std::min({K, k1 - k0, (uint64_t)0x7fffffffu >> lay.h});  // 32-bit queue tickets
+  CtxGuard guard;
+  int rc = guard.open(dev, "device buffers");
+  if (rc) return rc;
+  DeviceCtx* c = guard.c;
+  int occ = 0;
+  SUP_HIP(cplx_minors_occupancy(n, &occ));
+  if ((rc = ensure(c->d_cbtab, c->cbtab_cap, (size_t)K * (tab + 2 * NP)))) return rc;
+  if ((rc = ensure(c->d_chunk, c->chunk_cap, (size_t)K * 2 * per_chunks * n))) return rc;
+  if ((rc = ensure(c->d_cbout, c->cbout_cap, (size_t)K * 2 * n))) return rc;
+  if ((rc = ensure(c->d_cbidx, c->cbidx_cap, (size_t)K * 2 * n))) return rc;
+  if ((rc = ensure(c->d_cbU, c->cbU_cap, (size_t)2 * in.R * in.C))) return rc;
+  hipStream_t s = c->stream;
+  c->tables_uid = 0;  // the walk leaves head 0 nonzero
+  c->head_zero[0] = false;
+  SUP_HIP(hipMemcpyAsync(c->d_cbU, in.U, (size_t)2 * in.R * in.C * sizeof(double), hipMemcpyHostToDevice, s));
+  double* d_tabs = c->d_cbtab;
+  double* d_x0s = c->d_cbtab + (size_t)K * tab;
+  const uint64_t resident = (uint64_t)c->cus * (uint64_t)std::max(occ, 1);
+  const char* fg = std::getenv("SUP_WALK_GROUP");  // tests, read per call: chunks per ticket (the bits do not change)
+  double total_ms = 0.0;
+  for (uint64_t a = k0; a < k1; a += K) {
+    const uint64_t kk = std::min(K, k1 - a);
+    int32_t* d_rows = c->d_cbidx;
+    int32_t* d_cols = c->d_cbidx + (size_t)K * n;
+    SUP_HIP(hipMemcpyAsync(d_rows, in.rows + a * n, (size_t)kk * n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    SUP_HIP(hipMemcpyAsync(d_cols, in.cols + a * q, (size_t)kk * q * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    CplxBatchSrc src{};
+    src.U = c->d_cbU, src.rows = d_rows, src.cols = d_cols, src.C = in.C;
+    SUP_HIP(hipMemsetAsync(c->d_counter, 0, sizeof(unsigned), s));
+    const uint64_t chunks = range ? c1 - c0 : kk << lay.h;
+    const LaunchGeom geo =
+        walk_geometry(chunks, resident, kWavesPerBlock, false, fg ? std::max(1, std::atoi(fg)) : 0);
+    WalkParams p{};
+    p.cols = d_tabs;
+    p.x0 = d_x0s;
+    p.chunk_begin = range ? c0 : 0;
+    p.chunk_count = chunks;
+    p.L = lay.L;
+    p.m = lay.m;
+    p.n = n;
+    p.counter = c->d_counter;
+    p.group = geo.group;
+    p.chunk_out = c->d_chunk;
+    SUP_HIP(hipEventRecord(c->ev0, s));
+    SUP_ON_DEVICE(c->dev, "minors walk launch");
+    SUP_HIP(launch_cplx_minors_prepare(src, n, kk, d_tabs, d_x0s, s));
+    SUP_HIP(launch_cplx_minors(n, p, lay.h, (unsigned long long)per_chunks, (int)geo.grid, s));
+    if (!range) SUP_HIP(launch_cplx_batch_fold(c->d_chunk, q, lay.h, kk * (uint64_t)n, c->d_cbout, s));
+    SUP_HIP(hipEventRecord(c->ev1, s));
+    if (range)
+      SUP_HIP(hipMemcpyAsync(out, c->d_chunk, (size_t)2 * per_chunks * n * sizeof(double), hipMemcpyDeviceToHost, s));
+    else
+      SUP_HIP(hipMemcpyAsync(out + 2 * (a - k0) * n, c->d_cbout, (size_t)kk * 2 * n * sizeof(double),
+                             hipMemcpyDeviceToHost, s));
+    double ms = 0.0;
+    if ((rc = timed_sync(c, &ms))) return rc;
+    total_ms += ms;
+    if (grid_out) *grid_out = (int)geo.grid;
+  }
+  if (kernel_ms) *kernel_ms = total_ms;
+  return SUP_OK;
+}
+
+int run_cplx_minors(int dev, int n, const Layout& lay, const CplxBatchIn& in, uint64_t k0, uint64_t k1, double* out,
+                    double* kernel_ms, int* grid_out) {
+  return run_cplx_minors_impl(dev, n, lay, in, k0, k1, 0, 0, out, kernel_ms, grid_out);
+}
+
+int run_cplx_minors_range(int dev, int n, const Layout& lay, const CplxBatchIn& in, uint64_t c0, uint64_t c1,
+                          double* parts, double* kernel_ms, int* grid_out) {
+  if (c1 <= c0) {
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (grid_out) *grid_out = 0;
+    return SUP_OK;
+  }
+  return run_cplx_minors_impl(dev, n, lay, in, 0, 1, c0, c1, parts, kernel_ms, grid_out);
+}
+
 // Collision-aware complex walk (walk_cplxf.hip, cplx_fock.hip) of slab S on
 // device `dev`: U, the slab's index lists and its descriptor pools go up, then
 // prepare (tables and x(0) written on the device), the walk over the slab's

@@ -523,6 +523,39 @@ int run_cplx_batch(int dev, int n, const Layout& lay, const CplxBatchIn& in, uin
 int cplx_perman_batch(const CplxBatchIn& in, int n, uint64_t count, const sup_opts& o, bool on_cpu, double* out,
                       CplxInfo* info);
 
+// ---- one-walk permanent minors (cplx_minors.cpp; walk_cplxm.hip, cplx_minors.hip) ----
+// Matrix k of `in` (the submatrix form only) has n rows and n - 1 columns:
+// entry (j, c) = U[rows[k n + j]][cols[k (n-1) + c]].  The n minors of
+// matrices [k0, k1) (2 <= n <= 32, lay = the layout of order n - 1) into
+// out[2 ((k - k0) n + j) + {0, 1}] on device `dev`, bit-identical to the host
+// twin.  *kernel_ms: prepare + walk + fold kernel time summed over the slabs.
+int run_cplx_minors(int dev, int n, const Layout& lay, const CplxBatchIn& in, uint64_t k0, uint64_t k1, double* out,
+                    double* kernel_ms, int* grid = nullptr);
+// Matrix 0 of `in` alone: the wave-chunk partials of chunks [c0, c1), output
+// j's at parts[2 (j (c1 - c0) + c - c0) + {0, 1}].
+int run_cplx_minors_range(int dev, int n, const Layout& lay, const CplxBatchIn& in, uint64_t c0, uint64_t c1,
+                          double* parts, double* kernel_ms, int* grid = nullptr);
+// out[2 (k n + j)], [.. + 1] = the permanent of matrix k without row j, k <
+// count (sup_perman_complex_minors).  n = 1: ones; n <= 32: the one-walk sum;
+// n in 33..64: every minor materialised and run through cplx_perman.
+int cplx_minors(const CplxBatchIn& in, int n, uint64_t count, const sup_opts& o, bool on_cpu, double* out,
+                CplxInfo* info);
+// One raw n x (n-1) matrix (row-major interleaved), n in [2, 32]: per output
+// the pairwise tree over the partials of wave-chunks [c0, c1), not scaled
+// (sup_perman_complex_minors_range); out = 2 n doubles.
+int cplx_minors_range(const double* mat, int n, uint64_t c0, uint64_t c1, const sup_opts& o, bool on_cpu, double* out,
+                      CplxInfo* info);
+// nsamples boson-sampling outcomes (Clifford & Clifford 2018, algorithm A) of
+// n photons entering the M x M unitary U in the distinct modes `inputs`
+// (boson.cpp): out = nsamples x n output modes, ascending per sample.
+struct BosonInfo {
+  double kernel_ms = 0.0, minors_ms = 0.0, pmf_ms = 0.0;
+  int devices = 0;
+  uint64_t steps = 0;
+};
+int boson_sample(const double* U, int M, const int32_t* inputs, int n, uint64_t nsamples, uint64_t seed,
+                 const sup_opts& o, bool on_cpu, int32_t* out, BosonInfo* info);
+
 // ---- collision-aware complex permanents (cplx_fock.cpp; walk_cplxf.hip, cplx_fock.hip) ----
 // A slab of K matrices of order n as the walk reads it (cplx_fock.hpp): the
 // pools and descriptors, built on the host by cplx_fock.cpp.

@@ -85,7 +85,14 @@ SUP_DECL_CPLX(49)
 SUP_DECL_CPLXB(1)
 SUP_DECL_CPLXB(17)
 #undef SUP_DECL_CPLXB
-#define SUP_DECL_CPLXF(LO)                                                              \
+#define SUP_DECL_CPLXM(LO)                                                                                       \
+  hipError_t launch_cplxm_##LO(int n, const WalkParams& p, int hbits, unsigned long long ostride, int grid, \
+                               hipStream_t s);                                                               \
+  hipError_t occupancy_cplxm_##LO(int n, int* blocks_per_cu);
+SUP_DECL_CPLXM(1)
+SUP_DECL_CPLXM(17)
+#undef SUP_DECL_CPLXM
+#define SUP_DECL_CPLXF(LO)                                                             \
   hipError_t launch_cplxf_##LO(int n, const FockParams& p, int grid, hipStream_t s);   \
   hipError_t occupancy_cplxf_##LO(int n, int* blocks_per_cu);
 SUP_DECL_CPLXF(1)
@@ -163,6 +170,21 @@ hipError_t launch_cplx_batch_prepare(const CplxBatchSrc& src, int n, uint64_t K,
 // out[2k], out[2k + 1] = (4(n&1) - 2) x the pairwise tree over matrix k's
 // 2^hbits (re, im) partials at parts + 2 (k << hbits).
 hipError_t launch_cplx_batch_fold(const double* parts, int n, int hbits, uint64_t K, double* out, hipStream_t s);
+
+// One-walk permanent minors (walk_cplxm.hip, 2 <= n <= 32 rows, q = n - 1
+// columns): queue entry a walks global chunk p.chunk_begin + a, chunk
+// & (2^hbits - 1) of matrix >> hbits in the layout of order q.  p.cols / p.x0
+// = the matrices' tables (Re, then Im plane, each 2 max(q-1, 1) x NP) / start
+// vectors one after another; the partial of output j goes to
+// p.chunk_out[2 ((matrix n + j) ostride + a - (matrix << hbits))].
+hipError_t launch_cplx_minors(int n, const WalkParams& p, int hbits, unsigned long long ostride, int grid,
+                              hipStream_t s);
+hipError_t cplx_minors_occupancy(int n, int* blocks_per_cu);
+// The tables and start vectors of K such matrices from U (src.C its row
+// length) and the slab's index lists (rows K x n, cols K x (n - 1));
+// cplx_minors.hip.  src.mats is not used.
+hipError_t launch_cplx_minors_prepare(const CplxBatchSrc& src, int n, uint64_t K, double* tabs, double* x0s,
+                                      hipStream_t s);
 
 // Collision-aware complex walk (walk_cplxf.hip, n <= 64): the wave-chunks of a
 // slab of matrices in one queue, described by FockParams (cplx_fock.hpp).

@@ -6,13 +6,16 @@ profiles/complex/walk_cplx_resources.log: hipcc's
 -Rpass-analysis=kernel-resource-usage figures, then a scan of the -S output:
 the walk loop (the innermost loop with the most fp64 VALU instructions: one odd
 + one even Gray step, 2(6N - 2) of them; the collision-aware walk's loop is one
-step, 6N of them: 2N column adds, 4(N - 1) for the product, 4 for acc += w term)
+step, 6N of them: 2N column adds, 4(N - 1) for the product, 4 for acc += w term;
+the one-walk minors' loop is 2(16N - 24): per step 2N column adds, 12N - 24 for
+the prefix/suffix chain, 2N accumulates)
 with its scratch instructions, AGPR
 moves, v_mov and readlane / writelane, and the scratch instructions of the
 whole kernel.
 
   python tools/probes/cplx_resources.py batch > profiles/complex_batch/walk_cplx_batch_resources.log
   python tools/probes/cplx_resources.py fock > profiles/complex_fock/walk_cplx_fock_resources.log
+  python tools/probes/cplx_resources.py minors > profiles/complex_minors/walk_cplx_minors_resources.log
   python tools/probes/cplx_resources.py single --ranges 1_16 17_32   # walk_cplx<N>, to diff against its log
 """
 import argparse
@@ -25,9 +28,11 @@ import tempfile
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "superman_amd", "csrc")
 KERNELS = {"batch": ("walk_cplxb.hip", "walk_cplx_batch", ["1_16", "17_32"]),
            "single": ("walk_cplx.hip", "walk_cplx", ["1_16", "17_32", "33_48", "49_64"]),
+           "minors": ("walk_cplxm.hip", "walk_cplx_minors", ["1_16", "17_32"]),
            "fock": ("walk_cplxf.hip", "walk_cplx_fock", ["1_16", "17_32", "33_48", "49_64"])}
 # fp64 VALU instructions of the walk loop at order n, and how the logs name that count
-LOOP = {"fock": (lambda n: 6 * n, "6N", "one step")}
+LOOP = {"fock": (lambda n: 6 * n, "6N", "one step"),
+        "minors": (lambda n: 2 * (16 * n - 24), "2(16N-24)", "one odd + one even Gray step")}
 loop_f64, loop_name, loop_what = LOOP.get(sys.argv[1] if len(sys.argv) > 1 else "", (
     lambda n: 2 * (6 * n - 2), "2(6N-2)", "one odd + one even Gray step"))
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]

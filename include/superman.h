@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SUP_ABI_VERSION 15  /* 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
+#define SUP_ABI_VERSION 16  /* 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SUP_OK            0
@@ -213,7 +213,7 @@ int sup_perman_shard(const void* mat, sup_dtype t, int n, sup_kernel kernel, int
 /* The plan sup_perman would run with options `o` (NULL = defaults; o->jit and
  * o->gpu_num matter): walk kind (0 dense, 1 prefix/SpaRyser, 2 SkipPer,
  * 3 segmented), engine-bit -> column map (n-1 entries), lane and walk bits,
- * and (segmented walk) the walk bits held in every state (*cached_bits, 0-3)
+ * and (segmented walk) the walk bits held in every state (*cached_bits, 0-4)
  * and the pair bits with a specialised step (*pair_bits, 3-8; the walk loop is
  * unrolled by 2^pair_bits pair steps); *est_ops_per_step = the walk's cost
  * model (sup_stats.est_ops_per_step); any pointer may be NULL.  For the test
@@ -221,6 +221,29 @@ int sup_perman_shard(const void* mat, sup_dtype t, int n, sup_kernel kernel, int
 int sup_plan_info(const void* mat, sup_dtype t, int n, sup_kernel kernel, const sup_opts* o, int* walk_kind,
                   int* colmap, int* lane_bits, int* walk_bits, int* cached_bits, int* pair_bits,
                   double* est_ops_per_step);
+
+/* Op census of the plan sup_plan_info describes (ABI 16): the fp64 VALU
+ * operations per Gray step of the segmented walk's generated kernel, by class,
+ * counted from the generated statements.  census[0 .. SUP_CENSUS_CLASSES):
+ *    0 x^0 column adds of the specialised pair steps
+ *    1 derived row-copy adds              2 outer tree node re-forms
+ *    3 segment 0 tree node re-forms       4 D fmas
+ *    5 accumulates                        6 the two-level lane sum
+ *    7 generic shared step: column adds   8 its row-copy adds   9 its re-forms
+ *   10 specialised high-bit steps: column adds   11 their row-copy adds
+ *   12 their re-forms
+ * Classes 0..12 are the walk loop; added in index order they give
+ * sup_plan_info's *est_ops_per_step exactly.  Beside them, not in that sum:
+ *   13 chunk start and end, amortised over the chunk's 2^walk_bits Gray steps
+ * (est_ops_per_step prices the walk loop; the planner prices a chunk start on
+ * its own when it chooses the walk length).
+ * *hi_bits = the walk bits above the specialised pair bits that have
+ * straight-line steps of their own (the kernel's outer loop is unrolled by
+ * 2^hi_bits; SUP_JIT_HI forces it).  Other walk kinds: zeros, *hi_bits = 0.
+ * Any pointer may be NULL. */
+#define SUP_CENSUS_CLASSES 14
+int sup_plan_census(const void* mat, sup_dtype t, int n, sup_kernel kernel, const sup_opts* o, int* hi_bits,
+                    double* census);
 
 /* 64-bit fingerprint of the plan sup_perman / sup_perman_shard would run
  * with options `o` (walk kind, layout, engine column map, signed column

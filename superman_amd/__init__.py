@@ -20,7 +20,7 @@ from ._lib import (KERNEL_DENSE, KERNEL_SKIPPER, KERNEL_SPARYSER, LEAF_FN, SCHED
                    SCHED_STATIC, SupApproxResult, SupError, SupOpts, SupReduceOpts, SupStats)
 
 __all__ = [
-    "perman", "perman_cpu", "perman_exact", "perman_exact_range", "perman_quad", "perman_quad_range", "perman_complex", "perman_complex_range", "perman_complex_batch", "perman_complex_submatrices", "perman_complex_fock", "perman_complex_fock_plan", "perman_complex_minors", "perman_complex_minors_submatrices", "perman_complex_minors_range", "boson_sample", "read_mtx_complex", "partial", "perman_shard", "plan_info", "plan_key", "prepare", "read_matrix", "read_mtx", "sort_order",
+    "perman", "perman_cpu", "perman_exact", "perman_exact_range", "perman_quad", "perman_quad_range", "perman_complex", "perman_complex_range", "perman_complex_batch", "perman_complex_submatrices", "perman_complex_fock", "perman_complex_fock_plan", "perman_complex_minors", "perman_complex_minors_submatrices", "perman_complex_minors_range", "boson_sample", "read_mtx_complex", "partial", "perman_shard", "plan_info", "plan_census", "CENSUS_CLASSES", "plan_key", "prepare", "read_matrix", "read_mtx", "sort_order",
     "skip_order", "compress", "decompose", "perman_reduced", "approx", "grid_graph", "ALGOS_APPROX",
     "nw_start", "device_count", "rccl_devices", "layout", "ShardCall", "SupError", "ALGOS_DENSE", "ALGOS_SPARSE",
     "gpu_perman64_xshared_coalescing_mshared",
@@ -621,6 +621,30 @@ def plan_info(mat, kernel: str = "dense", jit: int = 0, gpu_num: int = 1, device
                                  C.byref(L), C.byref(m), C.byref(cc), C.byref(pb), C.byref(ops)), "plan_info")
     return {"kind": WALK_NAMES[kind.value], "colmap": cm[: n - 1].copy(), "L": L.value, "m": m.value,
             "cached": cc.value, "pair_bits": pb.value, "est_ops_per_step": ops.value}
+
+
+CENSUS_CLASSES = ("x_adds", "copy_adds", "outer_forms", "inner_forms", "d_fmas", "accumulates", "lane_sum",
+                  "shared_adds", "shared_copies", "shared_forms", "hi_adds", "hi_copies", "hi_forms")
+
+
+def plan_census(mat, kernel: str = "dense", jit: int = 0, gpu_num: int = 1, device_id: int = 0,
+                walk_log2: int = 0) -> dict:
+    """Op census of the plan plan_info describes (sup_plan_census): fp64 ops per
+    Gray step of the segmented walk's generated kernel by class ("classes": an
+    ordered dict over CENSUS_CLASSES, the walk loop, whose values added in
+    order give plan_info's est_ops_per_step exactly), "chunk_start" (the chunk
+    start and end amortised per Gray step, beside that sum) and "hi_bits", the
+    walk bits above the specialised pair bits that have straight-line steps of
+    their own."""
+    a, dt, n = _mat(mat)
+    lib = _lib.load()
+    hi = C.c_int()
+    cen = np.zeros(len(CENSUS_CLASSES) + 1, np.float64)
+    o = _opts(gpu_num=gpu_num, device_id=device_id, jit=jit, walk_log2=walk_log2)
+    _lib.check(lib.sup_plan_census(a.ctypes.data, dt, n, _KERNELS[kernel], C.byref(o), C.byref(hi), cen.ctypes.data),
+               "plan_census")
+    return {"hi_bits": hi.value, "classes": dict(zip(CENSUS_CLASSES, (float(v) for v in cen))),
+            "chunk_start": float(cen[-1])}
 
 
 def plan_key(mat, kernel: str = "dense", jit: int = 0, gpu_num: int = 1, device_id: int = 0,

@@ -33,7 +33,7 @@ SCHED_SINGLE, SCHED_STATIC, SCHED_CHUNKS, SCHED_MANUAL = 0, 1, 2, 3
 # Every symbol include/superman.h declares (checked by tests/test_capi.py).
 EXPORTS = [
     "sup_opts_init", "sup_abi_version", "sup_last_error", "sup_device_count", "sup_rccl_devices", "sup_device_checks", "sup_device_warmup", "sup_kernel_time",
-    "sup_perman", "sup_partial", "sup_perman_cpu", "sup_nw_start", "sup_perman_shard", "sup_plan_info",
+    "sup_perman", "sup_partial", "sup_perman_cpu", "sup_nw_start", "sup_perman_shard", "sup_plan_info", "sup_plan_census",
     "sup_prepare", "sup_plan_key", "sup_perman_exact", "sup_perman_exact_range", "sup_perman_reduced_exact",
     "sup_perman_quad", "sup_perman_quad_range",
     "sup_perman_reduced_quad", "sup_perman_complex", "sup_perman_complex_range", "sup_read_mtx_complex",
@@ -134,7 +134,7 @@ def load() -> C.CDLL:
             build()
         lib = C.CDLL(LIB_PATH)
         _declare(lib)
-        if lib.sup_abi_version() != 15:
+        if lib.sup_abi_version() != 16:
             raise RuntimeError("libsuperman_hip.so ABI version mismatch")
         _lib = lib
         return lib
@@ -181,6 +181,7 @@ def _declare(lib: C.CDLL) -> None:
     lib.sup_perman_shard.argtypes = [P, I, I, I, I, I, C.POINTER(SupOpts), C.POINTER(D), C.POINTER(SupStats)]
     lib.sup_plan_info.argtypes = [P, I, I, I, C.POINTER(SupOpts), C.POINTER(I), P, C.POINTER(I), C.POINTER(I),
                                   C.POINTER(I), C.POINTER(I), C.POINTER(D)]
+    lib.sup_plan_census.argtypes = [P, I, I, I, C.POINTER(SupOpts), C.POINTER(I), P]
     lib.sup_prepare.argtypes = [P, I, I, I, C.POINTER(SupOpts), C.POINTER(I), C.POINTER(C.c_double)]
     lib.sup_plan_key.argtypes = [P, I, I, I, C.POINTER(SupOpts), C.POINTER(C.c_uint64)]
     lib.sup_nw_start.argtypes = [P, I, I, C.POINTER(D), C.POINTER(D)]

@@ -650,6 +650,26 @@ int sup_plan_info(const void* mat, sup_dtype t, int n, sup_kernel kernel, const 
   return SUP_OK;
 }
 
+static_assert(SUP_CENSUS_CLASSES == kSegCensusN, "superman.h lists the census classes of engine.hpp");
+
+int sup_plan_census(const void* mat, sup_dtype t, int n, sup_kernel kernel, const sup_opts* o_in, int* hi_bits,
+                    double* census) {
+  std::vector<double> A;
+  int rc = to_double(mat, t, n, A);
+  if (rc) return rc;
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  Plan P;
+  if ((rc = check_walk_opts(o))) return rc;
+  if ((rc = plan_for(A.data(), n, kernel, layout_for(n, o), P, o.jit, o.gpu_num, o.device_id))) return rc;
+  const bool seg = P.kind == kWalkSeg;
+  if (hi_bits) *hi_bits = seg ? P.seg_hi : 0;
+  if (census)
+    for (int c = 0; c < kSegCensusN; ++c) census[c] = seg ? P.seg_census[c] : 0.0;
+  return SUP_OK;
+}
+
 int sup_plan_key(const void* mat, sup_dtype t, int n, sup_kernel kernel, const sup_opts* o_in, uint64_t* key) {
   if (!key) {
     set_error("sup_plan_key: key pointer missing");

@@ -36,6 +36,28 @@ void nw_start(const double* A, int n, double* x0, double* p0);
 // their per-state arrays for 2^4 states).
 constexpr int kMaxCachedBits = 4;
 
+// Classes of the segmented walk's op census (Plan::seg_census, fp64 VALU ops
+// per Gray step of the generated kernel; include/superman.h sup_plan_census
+// lists them in this order).  Counted from the generated statements.
+enum SegCensus {
+  kCenXAdd = 0,     // x^0 column adds of the specialised pair steps
+  kCenCopy,         // derived row-copy adds (live copies and copies formed inside a node)
+  kCenOuter,        // outer tree node re-forms
+  kCenInner,        // segment 0 tree node re-forms (x and y)
+  kCenD,            // D fmas (or subtractions)
+  kCenAcc,          // accumulates (one per pair step)
+  kCenLane,         // the two-level lane sum (tot += acc after every step of a walk bit > b)
+  kCenSharedAdd,    // generic shared step: column adds
+  kCenSharedCopy,   //   its row-copy adds
+  kCenSharedForm,   //   its node re-forms and D
+  kCenHiAdd,        // specialised high-bit steps: column adds
+  kCenHiCopy,       //   their row-copy adds
+  kCenHiForm,       //   their node re-forms and D
+  kCenStart,        // chunk start and end, amortised over the chunk's 2^m Gray steps: beside the walk
+                    // loop's classes above, which alone add up to Plan::seg_ops
+  kSegCensusN
+};
+
 // Walk layout for an n x n problem (depends on n only, so results are
 // bit-reproducible across grids and device counts).
 struct Layout {
@@ -105,7 +127,12 @@ struct Plan {
   bool lds = false;                // kWalkDense run by the LDS-staged kernel (walk_lds.hip; same bits)
   bool integral = false;           // every entry an integer (the segmented walk may then skip chunks)
   int seg_cc = 0;                  // cached step classes: walk bits 1..seg_cc held in every state
-  double seg_ops = 0.0;            // fp64 VALU ops per Gray step of the generated kernel
+  double seg_ops = 0.0;            // fp64 VALU ops per Gray step of the generated kernel (= the sum of seg_census's walk-loop classes)
+  double seg_model_ops = 0.0;      // seg_fit's count of the walk loop without high-bit steps: what the walk-length
+                                   // rule prices (make_seg_plan), so seg_hi never moves the layout
+  int seg_hi = 0;                  // the q loop is unrolled by 2^seg_hi: walk bits seg_b+1 .. seg_b+seg_hi get
+                                   // straight-line steps over their own rows (jit.cpp, "High-bit steps")
+  double seg_census[kSegCensusN] = {};  // seg_ops by class (SegCensus)
   double seg_skip = 0.0;           // sampled fraction of wave-chunks the kernel skips (integer matrices)
   int seg_regs = 0;                // values live across steps (doubles), estimate
   int seg_budget = 0;              // live-value budget the storage plan was fitted to
@@ -137,6 +164,7 @@ struct SegChoice {
   int b = 0;
   int budget = 0;
   int cc_cap = kMaxCachedBits;
+  int hi = 0;  // unrolled q bits (Plan::seg_hi)
 };
 
 // Build a plan.  identity_map keeps engine bit e = column e (needed when a
@@ -178,9 +206,9 @@ double seg_skip_fraction_plan(const Plan& P, int samples);
 std::vector<int> seg_row_order(const double* A, int n, const std::vector<int>& walk);
 // Fill the segment structure, packed table and generated source of a plan
 // whose rows are already in first-touch order (make_plan, kind kWalkSeg).
-// fixed_budget > 0: fit the storage plan to that live-value budget, no
-// compiler check (a recorded choice).
-int build_seg(Plan& P, int fixed_budget = 0);
+// fixed_budget > 0: fit the storage plan to that live-value budget and unroll
+// the q loop by 2^fixed_hi, no compiler check (a recorded choice).
+int build_seg(Plan& P, int fixed_budget = 0, int fixed_hi = 0);
 // Disk cache of segmented-walk choices (next to the code objects): key ->
 // (walk bits m, SegChoice).  jit_toolchain_hash() covers what the choices
 // were priced with (generated-code headers, compile options, hiprtc).

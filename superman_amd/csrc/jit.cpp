@@ -27,7 +27,29 @@
 // column, zeros included) — a switch over per-bit steps would make LLVM
 // carry copies of x across its arms (measured: 120 -> 242 VGPRs).
 //
-// Cached walk bits.  Walk bits 1..cc (cc <= 3, seg_best) are held in every
+// High-bit steps.  After block q the shared step flips walk bit
+// b + 1 + ctz(q + 1).  With the q loop unrolled by U = 2^u from an aligned q
+// (Plan::seg_hi = u, 0..3, at most m - 1 - b), U - 1 of every U of those steps
+// have a bit known when the code is generated — half of them b + 1, a quarter
+// b + 2, ... — and are straight-line code with no arms to join: each adds
+// its packed jtab values to its own rows only, re-derives the live copies of
+// those rows and re-forms the nodes above them (a subset of the shared
+// class's statements and constants, Gen::stmts_for / hi_loop).  Only the step
+// after the body's last block stays generic, over the rows of the walk bits
+// above b + u.  What is left out re-forms a value from unchanged inputs or
+// adds a zero to a row state that is never -0, so every
+// value, the classes, trees and the lane-sum order are those of u = 0; the
+// host twin and the mirror restate no u.  u is chosen after the order, b, cc
+// and the storage plan: the largest whose body (all U copies of the block)
+// stays under kMaxBlockBytes and whose op census total is lower, checked
+// against the compiler with the budget (build_seg); SUP_JIT_HI forces it.
+//
+// Op census.  The generated statements are counted by class while they are
+// emitted (Plan::seg_census, sup_plan_census, SUP_JIT_VERBOSE): the walk
+// loop's classes add up to Plan::seg_ops, the figure est_ops_per_step reports;
+// the chunk start, amortised over the chunk's steps, is reported beside them.
+//
+// Cached walk bits.  Walk bits 1..cc (cc <= kMaxCachedBits = 4, seg_best) are held in every
 // state: each node that depends on them has one copy per state of those
 // bits, so their pair steps only accumulate (the state is a compile-time
 // constant inside the unrolled block) and the other steps update every copy.
@@ -63,10 +85,10 @@
 // Debugging / experiment knobs: SUP_JIT_DUMP=<dir> keeps the generated source,
 // SUP_JIT_VERBOSE prints the plan's op count, live values and cached bits;
 // SUP_JIT_CC / _B / _STORAGE / _BUDGET / _STARTS / _POLISH / _REGMAX / _KP /
-// _PF / _XSTEP / _WAVES / _LDS force cached bits, pair bits, storage budget,
-// live-value budget (no compiler check), search starts, skip polish, register
-// budget, SGPR pieces per region, prefetch, cross-step regions, occupancy,
-// dynamic LDS.
+// _PF / _XSTEP / _WAVES / _LDS / _HI force cached bits, pair bits, storage
+// budget, live-value budget (no compiler check), search starts, skip polish,
+// register budget, SGPR pieces per region, prefetch, cross-step regions,
+// occupancy, dynamic LDS, unrolled q bits (high-bit steps).
 #include <dlfcn.h>
 #include <hip/hiprtc.h>
 #include <sched.h>
@@ -476,6 +498,10 @@ double seg_score(const SegFit& f) { return f.ops * (f.regs <= kRegs3 ? 1.0 : kOc
 // from the op count: 2 * ops per Gray step per pair step, 8 B per fp64 VOP3
 // instruction, +25% for the scalar loads, branches and sched barriers.  The
 // block must stay well inside the 64 KB instruction cache two CUs share.
+// With high-bit steps the loop body is 2^u copies of the block, the
+// specialised steps between them and the generic step: the guard covers that
+// whole body (Gen::block_bytes, counted from the generated statements; the
+// walk-order search prices the single block of u = 0 here).
 constexpr double kMaxBlockBytes = 40.0 * 1024.0;
 double seg_block_bytes(const SegFit& f, int b) { return 1.25 * 8.0 * 2.0 * f.ops * (double)(1u << b); }
 
@@ -950,9 +976,21 @@ std::vector<uint32_t> submasks(uint32_t m) {
 
 // A statement of a step whose operands may read constants of the step's
 // constant stream: "@<i>@" in `text` stands for the stream's i-th value.
+// What it re-forms (which steps need it: Gen::stmts_for) and its fp64 ops by
+// kind (the op census): row >= 0 a live copy of that row; node >= 0 node
+// `node` of tree ti; isD the D of one cached state.
 struct Stmt {
   std::string text;
+  int row = -1, ti = -1, node = -1;
+  bool isD = false;
+  int adds = 0, muls = 0, dops = 0;  // row-copy adds, node products, D's own fma / subtraction
 };
+
+int count_sub(const std::string& t, const char* pat) {
+  int c = 0;
+  for (size_t q = t.find(pat); q != std::string::npos; q = t.find(pat, q + 1)) ++c;
+  return c;
+}
 
 // Generated kernel (paired segmented walk).  Gray steps 2j and 2j+1 differ in
 // walk bit 0 only, so they are evaluated together: segment 0 (the rows walk
@@ -1109,24 +1147,57 @@ struct Gen {
           for (uint32_t S : submasks(rs(r))) {
             if (v == 0 && S == 0) continue;
             ks.push_back(cval(r, S, v));
-            st.push_back({cname(r, S, v) + " = x[" + std::to_string(r) + "] + @" + std::to_string(ks.size() - 1) +
-                          "@;"});
+            Stmt s{cname(r, S, v) + " = x[" + std::to_string(r) + "] + @" + std::to_string(ks.size() - 1) + "@;"};
+            s.row = r, s.adds = 1;
+            st.push_back(std::move(s));
           }
     auto upd = [&](int ti, int v) {
       const ProdTree& t = tr(ti);
       for (int i = 0; i < t.K(); ++i)
         if (((t.sig[i] >> c) & 1u) && nlive(ti, v, i))
-          for (uint32_t S : submasks(t.sig[i] & ccm))
-            st.push_back({nname(ti, v, i, S) + " = " + node(ti, v, i, S, &ks) + ";"});
+          for (uint32_t S : submasks(t.sig[i] & ccm)) {
+            Stmt s{nname(ti, v, i, S) + " = " + node(ti, v, i, S, &ks) + ";"};
+            s.ti = ti, s.node = i, s.adds = count_sub(s.text, " + @"), s.muls = count_sub(s.text, " * ");
+            st.push_back(std::move(s));
+          }
     };
     upd(0, 0);
     if ((P.inner_tree.root_sig() >> c) & 1u) {
       upd(1, 0);
       upd(1, 1);
-      for (uint32_t S : submasks(inner_root_csig()))
-        st.push_back({dname(S) + " = " +
-                      dexpr([&](int v, int id) { return opnd(1, v, id, S, &ks); }) + ";"});
+      for (uint32_t S : submasks(inner_root_csig())) {
+        Stmt s{dname(S) + " = " + dexpr([&](int v, int id) { return opnd(1, v, id, S, &ks); }) + ";"};
+        s.ti = 1, s.isD = true, s.dops = 1;
+        s.adds = count_sub(s.text, " + @"), s.muls = count_sub(s.text, " * ");
+        st.push_back(std::move(s));
+      }
     }
+  }
+
+  // The statements of the shared class a step over `rows` (a subset of
+  // dyn_rows) needs: the live copies of those rows, the nodes whose subtree
+  // holds one of them and D if segment 0's tree does, in the class's order.
+  // The others read nothing the step changed: they would re-form the value
+  // they already hold.  The constants stay those of the class's stream.
+  std::vector<Stmt> stmts_for(const std::vector<int>& rows) const {
+    std::vector<char> in(P.n, 0);
+    for (int r : rows) in[r] = 1;
+    std::vector<char> hit[2];
+    for (int ti = 0; ti < 2; ++ti) {
+      const ProdTree& t = tr(ti);
+      hit[ti].assign(t.items() + t.K(), 0);
+      for (int j = 0; j < t.items(); ++j) hit[ti][j] = t.item_row[j] >= 0 && in[t.item_row[j]];
+      for (int i = 0; i < t.K(); ++i) hit[ti][t.items() + i] = hit[ti][t.a[i]] || hit[ti][t.b[i]];
+    }
+    std::vector<Stmt> out;
+    for (const Stmt& s : cls_stmts[P.seg_b]) {
+      const bool need = s.row >= 0   ? (bool)in[s.row]
+                        : s.isD      ? P.inner_tree.root() >= 0 && hit[1][P.inner_tree.root()]
+                        : s.node >= 0 ? (bool)hit[s.ti][tr(s.ti).items() + s.node]
+                                      : true;
+      if (need) out.push_back(s);
+    }
+    return out;
   }
 
   // ---- straight-line code as a stream of items over SGPR pieces ----
@@ -1146,10 +1217,19 @@ struct Gen {
     std::string text;
     std::vector<int> pieces;
     int step = -1;  // pair step the item belongs to (-1: none)
+    std::string decl;  // declared before the loads of the item's region (a step's own table base)
   };
+  // Name of the opaque table base the current step's pieces load through
+  // (hi_loop: one per step); empty: the loop body's `jt`.
+  std::string step_base;
   std::vector<std::string> pieces;
   std::map<std::string, int> piece_id;
   int next_step_id = 0;
+  // fp64 ops of one pass through the q loop's body, by census class
+  double body[kSegCensusN] = {};
+  double census[kSegCensusN] = {};   // per Gray step (source())
+  double block_bytes = 0.0;          // instruction bytes of the q loop's body (source())
+  enum StepMode { kPairStep = 0, kSharedStep = 1, kHiStep = 2 };
   int piece(const std::string& load_expr) {
     auto it = piece_id.find(load_expr);
     if (it != piece_id.end()) return it->second;
@@ -1162,8 +1242,13 @@ struct Gen {
   // table at byte offset expression `off` from `base` for rows[i], or value
   // rows[i] of a full column, `full`), then the class's statements (row-copy
   // constants from its stream in jtab).
+  // `mode` names the census classes the step's ops count under; `stmts`
+  // replaces the class's statements (stmts_for: a step over some of its rows).
   void step_items(std::vector<Item>& out, const std::string& base, const std::string& off,
-                  const std::vector<int>& rows, bool full, int c) {
+                  const std::vector<int>& rows, bool full, int c, StepMode mode = kPairStep,
+                  const std::vector<Stmt>* stmts = nullptr) {
+    const int cen_add = mode == kPairStep ? kCenXAdd : (mode == kSharedStep ? kCenSharedAdd : kCenHiAdd);
+    const int cen_copy = mode == kPairStep ? kCenCopy : (mode == kSharedStep ? kCenSharedCopy : kCenHiCopy);
     auto col_piece = [&](int pc) {
       return piece("((cjdbl8*)(" + base + " + " + off + "))[" + std::to_string(pc) + "]");
     };
@@ -1171,9 +1256,17 @@ struct Gen {
     for (size_t i = 0; i < rows.size(); ++i) {
       const int vi = full ? rows[i] : (int)i, pc = col_piece(vi / 8);
       out.push_back({"x[" + std::to_string(rows[i]) + "] += " + pref(pc, vi % 8) + ";", {pc}, sid});
+      body[cen_add] += 1.0;
     }
     if (c < P.seg_cc) return;
-    for (const Stmt& st : cls_stmts[c]) {
+    for (const Stmt& st : stmts ? *stmts : cls_stmts[c]) {
+      body[cen_copy] += st.adds;
+      if (mode == kPairStep) {
+        body[st.ti == 0 ? kCenOuter : kCenInner] += st.muls;
+        body[kCenD] += st.dops;
+      } else {
+        body[mode == kSharedStep ? kCenSharedForm : kCenHiForm] += st.muls + st.dops;
+      }
       Item it;
       it.step = sid;
       const std::string& t = st.text;
@@ -1189,7 +1282,8 @@ struct Gen {
         // fresh opaque base: otherwise LLVM merges the two steps' loads of the
         // same piece and keeps them live across the block (SGPR spills)
         const bool fresh = std::getenv("SUP_JIT_FRESHBASE") && std::atoi(std::getenv("SUP_JIT_FRESHBASE"));
-        const std::string jb = own_stream[c] && !fresh ? "jt" : "(const char*)opaque_c(p.jtab, 0u)";
+        const std::string jb = own_stream[c] && !fresh ? (step_base.empty() ? std::string("jt") : step_base)
+                                                       : std::string("(const char*)opaque_c(p.jtab, 0u)");
         const int pc = piece("((cjdbl8*)(" + jb + " + " + std::to_string((cbase + pos - pos % 8) * 8) + "u))[0]");
         it.text += pref(pc, pos % 8);
         if (std::find(it.pieces.begin(), it.pieces.end(), pc) == it.pieces.end()) it.pieces.push_back(pc);
@@ -1272,6 +1366,8 @@ struct Gen {
       }
     auto pname = [&](size_t r, int pc) { return "s" + std::to_string(pc) + "_" + std::to_string(r); };
     auto load = [&](size_t r) {
+      for (size_t i = reg[r].first; i < reg[r].second; ++i)
+        if (!items[i].decl.empty()) o << ind << "  " << items[i].decl << "\n";
       for (int pc : rp[r]) o << ind << "  jdbl8 " << pname(r, pc) << " = " << pieces[pc] << ";\n";
     };
     // Pin at most kp pieces: a region holds one item that needs more (a
@@ -1428,6 +1524,97 @@ struct Gen {
     }
   }
 
+  // High-bit steps: the walk loop with its q loop unrolled by U = 2^u from an
+  // aligned q.  After block q the walk flips walk bit b + 1 + ctz(q + 1); with
+  // q = U qq + i that bit is b + 1 + ctz(i + 1) for i < U - 1, known when the
+  // code is generated: walk bits b+1 .. b+u get straight-line steps that add
+  // their packed jtab values to the rows they touch only, re-derive the live
+  // copies of those rows and re-form the nodes above them (stmts_for: a
+  // subset of the shared class's statements, reading its constant stream).
+  // The sign is ((q + 1) >> (kk + 1)) & 1: bit kk + 1 of i + 1 below bit u,
+  // bit 0 of qq at it.  Only the step after the body's last block is generic
+  // (kk >= u, dynamic column), over the rows of the walk bits above b + u.
+  // Every step that is left out re-forms a value from unchanged inputs, and
+  // every add that is left out adds a zero of the signed column to a row
+  // state that is never -0 (build_seg takes u = 0 if a start value is): the
+  // values, the accumulate chain and the lane sum are those of u = 0.
+  // Each step has its own opaque table base: through one base per body LLVM
+  // merges the loads of a piece that several steps of a class read and holds
+  // it in SGPRs across the longer body (measured on the n = 40 bench plan at
+  // u = 1: 202 v_readlane reloads of spilled pieces in the loop, against 16
+  // in the plain loop).
+  void hi_loop(unsigned Q, unsigned U, int u) {
+    const int L = P.lay.L, m = P.lay.m, b = P.seg_b, cc = P.seg_cc;
+    const unsigned B = 1u << b;
+    o << "      for (uint32_t qq = 0; qq < " << Q / U << "u; ++qq) {\n";
+    const char* ind = "        ";
+    o << ind << "const uint32_t ngh = qq & 1u;\n";
+    for (unsigned i = 0; i < U; ++i) {
+      o << ind << "{\n";
+      std::vector<Item> items;
+      // a step's pieces load through a base of its own, declared with its
+      // region's loads
+      auto own_base = [&](size_t first) {
+        if (items.size() > first)
+          items[first].decl = "const char* " + step_base + " = (const char*)opaque_c(p.jtab, 0u);";
+        step_base.clear();
+      };
+      for (unsigned st = 1; st < B; ++st) {
+        const int pb = __builtin_ctz(st), k = pb + 1;
+        if (pb >= cc && !P.touched[k].empty()) {  // the top pair bit's sign is bit 0 of q = U qq + i: of i
+          const size_t first = items.size();
+          step_base = "jt" + std::to_string(next_step_id);
+          step_items(items, step_base, off_const(k, pb < b - 1 ? (st >> (pb + 1)) & 1u : i & 1u), P.touched[k],
+                     false, step_class(k, b));
+          own_base(first);
+        }
+        items.push_back({accumulate_text(st & 1u, state(st)), {}});
+        body[kCenAcc] += 1.0;
+      }
+      if (i + 1 < U) {
+        const int kk = __builtin_ctz(i + 1), k = b + 1 + kk;
+        const std::vector<Stmt> st = stmts_for(P.touched[k]);
+        const size_t first = items.size();
+        step_base = "jt" + std::to_string(next_step_id);
+        step_items(items, step_base, kk + 1 < u ? off_const(k, ((i + 1) >> (kk + 1)) & 1u) : off_dyn(k, "ngh"),
+                   P.touched[k], false, b, kHiStep, &st);
+        own_base(first);
+        items.push_back({accumulate_text(false, 0u), {}});
+        items.push_back({"tot += acc;", {}});
+        items.push_back({"acc = 0.0;", {}});
+        body[kCenAcc] += 1.0, body[kCenLane] += 1.0;
+      }
+      emit_items(items, ind);
+      o << ind << "}\n";
+    }
+    body[kCenAcc] += 1.0;  // the pair after the body's last block: the generic step's, or the chunk start's
+    if (Q > U) {
+      std::vector<int> rows;
+      {
+        std::vector<char> in(P.n, 0);
+        for (int k = b + u + 1; k < m; ++k)
+          for (int r : P.touched[k]) in[r] = 1;
+        for (int r = 0; r < P.n; ++r)
+          if (in[r]) rows.push_back(r);
+      }
+      const std::vector<Stmt> st = stmts_for(rows);
+      o << ind << "if (qq + 1u < " << Q / U << "u) {\n";
+      o << ind << "  const char* jt = (const char*)opaque_c(p.jtab, 0u);\n";
+      o << ind << "  const uint32_t kk = (uint32_t)__builtin_ctz(qq + 1u);\n";
+      o << ind << "  const uint32_t ngd = ((qq + 1u) >> (kk + 1u)) & 1u;\n";
+      std::vector<Item> items;
+      step_items(items, "(const char*)opaque_c(p.cols, 0u)",
+                 "(2u * (" + std::to_string(L + b + 1 + u) + "u + kk) + ngd) * " + std::to_string(P.NP * 8) + "u",
+                 rows, true, b, kSharedStep, &st);
+      items.push_back({accumulate_text(false, 0u), {}});
+      emit_items(items, "          ");
+      o << ind << "  tot += acc;\n" << ind << "  acc = 0.0;\n";
+      body[kCenLane] += 1.0;
+      o << ind << "}\n";
+    }
+    o << "      }\n";
+  }
+
   std::string source() {
     const int n = P.n, L = P.lay.L, m = P.lay.m, b = P.seg_b, cc = P.seg_cc;
     const unsigned B = 1u << b, Q = 1u << (m - 1 - b);
@@ -1551,6 +1738,7 @@ struct Gen {
     o << "      const uint64_t a = base + j;\n";
     o << "      if (a >= p.chunk_count) break;\n";
     o << "      const uint64_t ga = p.chunk_begin + a;\n";
+    const size_t start_begin = o.str().size();
     o << "      double x[N], y[" << len0 << "];\n";
     if (trace) o << "      const uint64_t tr_s = __builtin_amdgcn_s_memtime();\n";
     o << "      chunk_start" << (P.start_tab_on ? "_tab" : "") << "<N>(x, p, ga, SUP_LANE());\n";
@@ -1605,6 +1793,12 @@ struct Gen {
     // no sequential sum runs longer than 2^b pairs (error growth, HISTORY.md §3.3 "Lane sum")
     o << "      double tot = 0.0;\n";
     if (trace) o << "      asm volatile(\"\" : \"+v\"(acc));\n      tr_sc += __builtin_amdgcn_s_memtime() - tr_s;\n      ++tr_n;\n";
+    const int u = std::max(0, std::min(P.seg_hi, m - 1 - b));
+    const unsigned U = 1u << u;
+    const size_t start_end = o.str().size();  // the chunk start's text ends here (the op census)
+    if (u > 0) {
+      hi_loop(Q, U, u);
+    } else {
     o << "      for (uint32_t q = 0; q < " << Q << "u; ++q) {\n";
     const char* ind = "        ";
     // pair index j = B*q + s, s = 1 .. B-1: pair bit p = ctz(s) (walk bit p+1);
@@ -1623,9 +1817,11 @@ struct Gen {
           step_items(items, "jt", pb < b - 1 ? off_const(k, (st >> (pb + 1)) & 1u) : off_dyn(k, "ng"),
                      P.touched[k], false, step_class(k, b));
         items.push_back({accumulate_text(st & 1u, state(st)), {}});
+        body[kCenAcc] += 1.0;
       }
       emit_items(items, ind);
     }
+    body[kCenAcc] += 1.0;  // the pair the shared step (or, once per chunk, the chunk start) accumulates
     if (Q > 1) {
       // j = B(q+1): pair bit b + ctz(q+1) (walk bit b+1+ctz(q+1)), neg =
       // ((q+1) >> (ctz(q+1)+1)) & 1.  One straight-line step for all of them
@@ -1639,14 +1835,38 @@ struct Gen {
         std::vector<Item> items;
         step_items(items, "(const char*)opaque_c(p.cols, 0u)",
                    "(2u * (" + std::to_string(L + b + 1) + "u + kk) + ngd) * " + std::to_string(P.NP * 8) + "u",
-                   P.dyn_rows, true, P.seg_b);
+                   P.dyn_rows, true, P.seg_b, kSharedStep);
         items.push_back({accumulate_text(false, 0u), {}});
         emit_items(items, "          ");
       }
       o << ind << "  tot += acc;\n" << ind << "  acc = 0.0;\n";
+      body[kCenLane] += 1.0;
       o << ind << "}\n";
     }
     o << "      }\n";
+    }
+    // The op census: the body's ops over its 2 U 2^b Gray steps (the generic
+    // step at the full weight of one per body, as seg_fit prices the shared
+    // class: it is skipped once per chunk).  Beside the walk loop's classes,
+    // not in their sum (seg_ops has always priced the walk loop; the
+    // walk-length rule prices a chunk start on its own, kSegStartOps): the
+    // chunk start and end — every fp64 operation of the generated text up to
+    // the walk loop, the start state's column adds (L lane columns; half the
+    // chunk bits' columns unless the start table holds them), the final
+    // tot + acc and wave_sum's six adds — over the chunk's 2^m Gray steps.
+    {
+      const double steps = 2.0 * (double)U * (double)B;
+      double walk = 0.0;
+      for (int c = 0; c < kCenStart; ++c) census[c] = body[c] / steps, walk += body[c];
+      const std::string init = o.str().substr(start_begin, start_end - start_begin);
+      const double start_ops = count_sub(init, " + ") + count_sub(init, " * ") + count_sub(init, " - ") +
+                               count_sub(init, "__builtin_fma(") + 7.0 +
+                               (double)n * ((double)L + (P.start_tab_on ? 0.0 : 0.5 * (double)(n - 1 - L - m)));
+      census[kCenStart] = std::ldexp(start_ops, -m);
+      // 8 B per fp64 VOP3 instruction, +25% for the scalar loads, branches and
+      // scheduling barriers (seg_block_bytes prices a plan the same way)
+      block_bytes = 1.25 * 8.0 * walk;
+    }
     o << "      acc = tot + acc;\n";
     o << "      if (((uint32_t)ga ^ (uint32_t)__builtin_popcount(SUP_LANE())) & 1u) acc = -acc;\n";
     o << "      }\n";
@@ -1785,7 +2005,7 @@ static void seg_start_table(Plan& P) {
   });
 }
 
-int build_seg(Plan& P, int fixed_budget) {
+int build_seg(Plan& P, int fixed_budget, int fixed_hi) {
   const int n = P.n, L = P.lay.L, m = P.lay.m;
   if (m < 3) {
     set_error("segmented walk needs >= 3 walk bits");
@@ -1873,7 +2093,14 @@ int build_seg(Plan& P, int fixed_budget) {
   // trees, cached classes and storage plan for live-value budget `budget`,
   // then the tables and the generated source (Q starts as a copy of P)
   const int cc_cap = std::min(max_cached(), P.lay.cc_cap);
-  auto finish = [&SR, &cc_cap, n, L, m](Plan& Q, int budget) {
+  // hi: the unrolled q bits (Plan::seg_hi), clamped to m - 1 - b; -1 = the
+  // largest of 0..3 whose loop body (all 2^hi copies of the block) stays under
+  // kMaxBlockBytes and whose census total is below that of 0.  SUP_JIT_HI
+  // forces a value (tests, experiments).  A start value that is a negative
+  // zero (a -0.0 entry in the last column of a row that sums to zero) takes 0:
+  // the high-bit steps leave out adds of zeros, which keep every bit only
+  // while no row state is -0 (Gen::hi_loop).
+  auto finish = [&SR, &cc_cap, n, L, m](Plan& Q, int budget, int hi) {
     SegFit f;
     // experiments / tests: SUP_JIT_CC forces cc; SUP_JIT_STORAGE forces the
     // storage budget of the chosen plan (same walk order and trees, other
@@ -1885,7 +2112,7 @@ int build_seg(Plan& P, int fixed_budget) {
     Q.outer_tree = std::move(f.outer);
     Q.inner_tree = std::move(f.inner);
     Q.seg_cc = f.cc;
-    Q.seg_ops = f.ops;
+    Q.seg_model_ops = f.ops;
     Q.seg_regs = f.regs;
     Q.seg_budget = budget;
     Q.jofs.assign(m, 0);
@@ -1903,20 +2130,52 @@ int build_seg(Plan& P, int fixed_budget) {
     Q.seg_cbase = Q.jtab.size();
     Q.seg_kp = 4;
     if (const char* e = std::getenv("SUP_JIT_KP")) Q.seg_kp = std::max(1, std::atoi(e));
-    Gen g(Q);
-    Q.jit_src = g.source();
+    const int hi_max = std::min(3, m - 1 - Q.seg_b);
+    if (const char* e = std::getenv("SUP_JIT_HI")) hi = std::max(0, std::min(3, std::atoi(e)));
+    bool neg_zero = false;
+    for (int j = 0; j < n; ++j) neg_zero = neg_zero || (Q.x0[j] == 0.0 && std::signbit(Q.x0[j]));
+    if (neg_zero) hi = 0;
+    // the generated source, census and constant tail with `h` unrolled q bits
+    auto generate = [&Q](int h, std::string* src) {
+      Q.seg_hi = h;
+      auto g = std::make_unique<Gen>(Q);
+      *src = g->source();
+      return g;
+    };
+    auto total = [](const Gen& g) {  // the walk loop's classes, in index order (Plan::seg_ops)
+      double ops = 0.0;
+      for (int c = 0; c < kCenStart; ++c) ops += g.census[c];
+      return ops;
+    };
+    int taken = hi < 0 ? 0 : std::min(hi, hi_max);
+    std::string src;
+    std::unique_ptr<Gen> g = generate(taken, &src);
+    for (int h = hi < 0 ? hi_max : 0; h > 0; --h) {
+      std::string s2;
+      std::unique_ptr<Gen> gh = generate(h, &s2);
+      if (gh->block_bytes <= kMaxBlockBytes && total(*gh) < total(*g)) {
+        g = std::move(gh), src = std::move(s2), taken = h;
+        break;
+      }
+    }
+    Q.seg_hi = taken;
+    Q.jit_src = std::move(src);
+    for (int c = 0; c < kSegCensusN; ++c) Q.seg_census[c] = g->census[c];
+    Q.seg_ops = total(*g);
     {
-      const std::vector<double> t = g.tail();
+      const std::vector<double> t = g->tail();
       Q.jtab.insert(Q.jtab.end(), t.begin(), t.end());
     }
     Q.jit_key = jit_source_key(Q.jit_src);
-    (void)n;
   };
   // SUP_JIT_BUDGET (experiments) or a recorded choice: this budget, no
   // compiler check
   const char* env_budget = std::getenv("SUP_JIT_BUDGET");
+  // a plan the compiler does not check keeps the plain q loop (a recorded
+  // choice: what its check chose)
+  const int hi_unchecked = fixed_budget > 0 ? fixed_hi : 0;
   if (env_budget) fixed_budget = std::max(1, std::atoi(env_budget));
-  finish(P, fixed_budget > 0 ? fixed_budget : kRegsMax);
+  finish(P, fixed_budget > 0 ? fixed_budget : kRegsMax, hi_unchecked);
   // The live-value budget against the compiler (walks of 10 ms or more).  The
   // estimate is rough: on the n = 40 bench matrix budgets up to 192 compile
   // without a spill, 194-216 spill 5-13 VGPRs, 218+ 17-27; denser or larger
@@ -1950,12 +2209,14 @@ int build_seg(Plan& P, int fixed_budget) {
     CodeScan s;
     P.seg_loop_scratch = jit_code_scan(P, &s) != SUP_OK || s.loop_scratch != 0;
   }
-  if (!fixed && walk_s >= 0.01 && P.seg_regs > kRegs3) {
+  // The ladder with `hi` unrolled q bits (-1: finish's rule per budget) into
+  // `out`: SUP_OK, or SUP_EHIP when no budget's kernel is acceptable.
+  auto ladder = [&](int hi, Plan& out) -> int {
     // the ladder of budgets, one candidate plan per budget (host threads)
     std::vector<int> budgets;
     for (int b2 = kRegs3 + 20; b2 <= kRegsMax + 60; b2 += 8) budgets.push_back(b2);
     std::vector<Plan> cand(budgets.size(), P);
-    parallel_tasks(budgets.size(), [&](size_t i) { finish(cand[i], budgets[i]); });
+    parallel_tasks(budgets.size(), [&](size_t i) { finish(cand[i], budgets[i], hi); });
     // distinct kernels in budget order
     std::vector<size_t> idx;
     for (size_t i = 0; i < cand.size(); ++i) {
@@ -2063,7 +2324,7 @@ int build_seg(Plan& P, int fixed_budget) {
                    : scans[k].scratch_bytes ? kCleanScratch
                                             : kClean0;
     }
-    if (outcome[idx[pp]] == kFail) return SUP_EHIP;  // the probe's compile error is set
+    if (outcome[idx[pp]] == kFail) return (int)SUP_EHIP;  // the probe's compile error is set
     auto pick = [&]() {
       int c = -1, bare = -1;
       for (size_t i : idx) {
@@ -2077,15 +2338,43 @@ int build_seg(Plan& P, int fixed_budget) {
     if (std::getenv("SUP_JIT_VERBOSE"))
       for (size_t i : idx)
         if (done[i])
-          std::fprintf(stderr, "  budget %d: ops %.4f rc %d vgprs %d spills %d scratch %dB (loop %d of %d insts, %d readlane)%s\n",
-                       budgets[i], cand[i].seg_ops, src[i], scans[i].vgprs, scans[i].vgpr_spills,
+          std::fprintf(stderr, "  budget %d hi %d: ops %.4f rc %d vgprs %d spills %d scratch %dB (loop %d of %d insts, %d readlane)%s\n",
+                       budgets[i], cand[i].seg_hi, cand[i].seg_ops, src[i], scans[i].vgprs, scans[i].vgpr_spills,
                        scans[i].scratch_bytes, scans[i].loop_scratch, scans[i].loop_insts, scans[i].loop_readlane,
                        (int)i == best ? "  <- chosen" : "");
     if (best < 0) {
       set_error("segmented walk: every budget's kernel touches scratch inside its walk loop (or fails to compile)");
-      return SUP_EHIP;
+      return (int)SUP_EHIP;
     }
-    P = std::move(cand[best]);
+    out = std::move(cand[best]);
+    return SUP_OK;
+  };
+  if (!fixed && walk_s >= 0.01 && P.seg_regs > kRegs3) {
+    // The unrolled q loop is part of the candidate: the ladder runs with
+    // finish's choice of high-bit steps per budget.  Its body is larger, so it
+    // may only stay free of scratch at a lower budget; the plain loop's ladder
+    // runs too unless even its cheapest plan (the largest budget, compiled or
+    // not) has more ops than the kernel chosen, and the one with fewer ops is
+    // taken (ties: the plain loop).
+    Plan best_hi, best_0;
+    const int rc_hi = ladder(-1, best_hi);
+    int rc_0 = SUP_EHIP;
+    bool need_0 = rc_hi != SUP_OK || best_hi.seg_hi == 0;
+    if (!need_0) {
+      Plan top = P;
+      finish(top, kRegsMax + 60, 0);
+      need_0 = top.seg_ops <= best_hi.seg_ops;
+    }
+    if (rc_hi == SUP_OK && best_hi.seg_hi == 0) rc_0 = SUP_OK, best_0 = best_hi, need_0 = false;
+    else if (need_0) rc_0 = ladder(0, best_0);
+    if (rc_hi != SUP_OK && rc_0 != SUP_OK) return SUP_EHIP;
+    const bool take_hi = rc_hi == SUP_OK && (rc_0 != SUP_OK || best_hi.seg_ops < best_0.seg_ops);
+    if (std::getenv("SUP_JIT_VERBOSE"))
+      std::fprintf(stderr, "  high-bit steps: %s (unrolled ladder %s hi %d ops %.4f; plain ladder %s ops %.4f)\n",
+                   take_hi ? "taken" : "not taken", rc_hi == SUP_OK ? "ok" : "failed", best_hi.seg_hi,
+                   rc_hi == SUP_OK ? best_hi.seg_ops : 0.0,
+                   rc_0 == SUP_OK ? "ok" : (need_0 ? "failed" : "not needed"), rc_0 == SUP_OK ? best_0.seg_ops : 0.0);
+    P = std::move(take_hi ? best_hi : best_0);
   }
   P.seg_skip = seg_skip_fraction_plan(P, 2048);
   if (P.start_tab_on) seg_start_table(P);
@@ -2094,6 +2383,17 @@ int build_seg(Plan& P, int fixed_budget) {
                  "(storage plans evaluated: %ld)\n", n, m, P.seg_b, P.seg_ops, P.seg_regs, P.seg_cc,
                  P.jtab.size() * sizeof(double), P.seg_cbase * sizeof(double), (unsigned long long)P.jit_key,
                  g_fit_calls.load());
+  if (std::getenv("SUP_JIT_VERBOSE")) {
+    const double* c = P.seg_census;
+    std::fprintf(stderr,
+                 "  op census (fp64 ops per Gray step, hi=%d): x adds %.4f, copy adds %.4f, outer forms %.4f, "
+                 "segment-0 forms %.4f, D %.4f, accumulates %.4f, lane sum %.4f, shared step adds %.4f copies %.4f "
+                 "forms %.4f, high-bit steps adds %.4f copies %.4f forms %.4f; total %.4f (storage fit's count of the "
+                 "plain walk loop without the lane sum %.4f); beside it, chunk start %.4f\n",
+                 P.seg_hi, c[kCenXAdd], c[kCenCopy], c[kCenOuter], c[kCenInner], c[kCenD], c[kCenAcc], c[kCenLane],
+                 c[kCenSharedAdd], c[kCenSharedCopy], c[kCenSharedForm], c[kCenHiAdd], c[kCenHiCopy], c[kCenHiForm],
+                 P.seg_ops, P.seg_model_ops, c[kCenStart]);
+  }
   return SUP_OK;
 }
 

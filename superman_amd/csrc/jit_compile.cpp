@@ -450,7 +450,7 @@ uint64_t jit_toolchain_hash() {
 }
 
 // Recorded segmented-walk choices: a small text file next to the code objects,
-// "supseg 3 <m> <b> <budget> <cc cap> <count> <order...>".
+// "supseg 4 <m> <b> <budget> <cc cap> <unrolled q bits> <count> <order...>".
 bool seg_choice_load(uint64_t key, int* m, SegChoice* c) {
   const std::string dir = cache_dir();
   if (dir.empty()) return false;
@@ -460,8 +460,8 @@ bool seg_choice_load(uint64_t key, int* m, SegChoice* c) {
   std::istringstream in(buf.data());
   std::string tag;
   int ver = 0, cnt = 0;
-  if (!(in >> tag >> ver >> *m >> c->b >> c->budget >> c->cc_cap >> cnt) || tag != "supseg" || ver != 3 || cnt < 1 ||
-      cnt > 64 || c->cc_cap < 0 || c->cc_cap > kMaxCachedBits)
+  if (!(in >> tag >> ver >> *m >> c->b >> c->budget >> c->cc_cap >> c->hi >> cnt) || tag != "supseg" || ver != 4 || cnt < 1 ||
+      cnt > 64 || c->hi < 0 || c->hi > 3 || c->cc_cap < 0 || c->cc_cap > kMaxCachedBits)
     return false;
   c->order.resize(cnt);
   for (int& v : c->order)
@@ -479,7 +479,7 @@ void seg_choice_store(uint64_t key, int m, const SegChoice& c) {
   const std::string dir = cache_dir();
   if (dir.empty() || c.order.empty()) return;
   std::ostringstream o;
-  o << "supseg 3 " << m << ' ' << c.b << ' ' << c.budget << ' ' << c.cc_cap << ' ' << c.order.size();
+  o << "supseg 4 " << m << ' ' << c.b << ' ' << c.budget << ' ' << c.cc_cap << ' ' << c.hi << ' ' << c.order.size();
   for (int v : c.order) o << ' ' << v;
   o << '\n';
   const std::string str = o.str();

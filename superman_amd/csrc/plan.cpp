@@ -552,7 +552,7 @@ int make_plan(const double* A, int n, WalkKind kind, bool identity_map, const La
     if ((kind == kWalkSparse || kind == kWalkDense) && !lane_touched && rm == 0 && !no_chunk_ends())
       P.chunk_ends |= 1ull << j;
   }
-  if (kind == kWalkSeg) return build_seg(P, choice ? choice->budget : 0);
+  if (kind == kWalkSeg) return build_seg(P, choice ? choice->budget : 0, choice ? choice->hi : 0);
   return SUP_OK;
 }
 
@@ -676,7 +676,7 @@ static int make_seg_plan(const double* A, int n, const Layout& lay, Plan& P) {
   if (!lay.fixed) {
     const int mmax = std::min(lay.m + lay.h - kSegMinChunkBits, 31);
     int m2 = lay.m;
-    while (m2 < mmax && std::ldexp(walk_cost(P), m2) < 32.0 * kSegStartOps) ++m2;
+    while (m2 < mmax && std::ldexp(P.seg_model_ops, m2) < 32.0 * kSegStartOps) ++m2;
     if (m2 != lay.m) {
       Layout l2 = lay;
       l2.m = m2;
@@ -684,7 +684,7 @@ static int make_seg_plan(const double* A, int n, const Layout& lay, Plan& P) {
       Plan s2;
       if (plan(l2, s2) == SUP_OK) {
         auto eff = [](const Plan& q) {
-          return (1.0 - q.seg_skip) * (walk_cost(q) + std::ldexp(kSegStartOps, -q.lay.m));
+          return (1.0 - q.seg_skip) * (q.seg_model_ops + std::ldexp(kSegStartOps, -q.lay.m));
         };
         if (eff(s2) < eff(P)) P = std::move(s2);
       }
@@ -694,6 +694,7 @@ static int make_seg_plan(const double* A, int n, const Layout& lay, Plan& P) {
   c.order = P.seg_order;
   c.b = P.seg_b;
   c.budget = P.seg_budget;
+  c.hi = P.seg_hi;
   c.cc_cap = P.lay.cc_cap;
   seg_choice_store(dkey, P.lay.m, c);
   // what this cold plan cost (search + the compiler check's compiles): auto

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SUP_ABI_VERSION 16  /* 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
+#define SUP_ABI_VERSION 17  /* 17: sup_perman_complex_fock_minors, sup_perman_complex_fock_minors_plan, sup_boson_sample_fock; 16: sup_plan_census; 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SUP_OK            0
@@ -534,6 +534,54 @@ int sup_perman_complex_minors_range(const double* mat, int n, uint64_t c0, uint6
  * stage. */
 int sup_boson_sample(const double* U, int M, const int32_t* inputs, int n, uint64_t nsamples, uint64_t seed,
                      const sup_opts* o, int on_cpu, int32_t* out /* nsamples x n, ascending modes */, sup_stats* st);
+
+/* Collision-aware form of sup_perman_complex_minors (ABI 17): the same
+ * arguments, index checks, messages, count == 0, null-pointer and SUP_ENODEV
+ * behaviour, but the repeated columns of B are collapsed as
+ * sup_perman_complex_fock collapses them.  B[i][c] =
+ * U[rows[k*n + i]][cols[k*(n-1) + c]]; with the distinct columns b_k (vectors
+ * over all n rows) of multiplicities t_k (order of first appearance, sum
+ * n - 1), one copy of the rarest group held (the first on a tie; t'_k =
+ * t_k - 1 there, t_k else),
+ *   x_i(v) = 1/2 sum_k (t_k - 2 v_k) b_k[i]
+ *   per(B without row j) = 2 sum_{0 <= v_k <= t'_k} (-1)^(sum v) prod_k C(t'_k, v_k) prod_{i != j} x_i(v),
+ * T = prod (t'_k + 1) terms instead of 2^(n-2), and since x_i(v) depends on row
+ * i only, one walk serves all n minors: 16n - 20 fp64 operations per walked
+ * state.  Only the column side is collapsed; repeated rows are only gathered.
+ * The layout is sup_perman_complex_fock's rule on the column multiplicities.
+ * n in [1, 32] (larger: SUP_EUNSUPPORTED; n < 1: SUP_EINVAL); n = 1: the one
+ * minor is 1 + 0i, no device work (cols may be NULL only here).
+ * Result (k, j) is a function of (U, rows[k], cols[k]) only: bit-identical on
+ * the GPU (per slab three launches and one download: tables and start vectors
+ * written on the device, walk_cplxfm.hip over one queue of the wave-chunks of
+ * all its matrices, a fold per output), on any device count, for any slab size
+ * (256 MiB; the environment variable SUP_CPLX_FOCK_MINORS_SLAB=<matrices>
+ * overrides it, for tests) and on o->threads host threads (on_cpu = 1).  It
+ * does NOT have sup_perman_complex_minors' bits.  o->gpu_num devices from
+ * o->device_id take contiguous ranges of matrices; o->walk_log2 is checked and
+ * otherwise unused.
+ * st: leaves = count n, gray_steps = count 2^(n-2) (nominal; 0 at n = 1),
+ * visited_steps = sum_k T_k (0 at n = 1: nothing is walked), kernel_ms,
+ * wall_ms, devices_used, grid, est_ops_per_step = 16n - 20. */
+int sup_perman_complex_fock_minors(const double* U, int R, int C, const int32_t* rows, const int32_t* cols,
+                                   int n, uint64_t count, const sup_opts* o, int on_cpu, double* out,
+                                   sup_stats* st);
+/* The terms T of that sum per matrix, host only: cols = count x (n-1) (indices
+ * only compared, not range-checked), terms[k] = T_k (1 at n = 1 and n = 2).
+ * n < 1, null terms, or null cols with n != 1: SUP_EINVAL; n > 32:
+ * SUP_EUNSUPPORTED. */
+int sup_perman_complex_fock_minors_plan(const int32_t* cols, int n, uint64_t count, uint64_t* terms);
+/* sup_boson_sample with every stage's minors from
+ * sup_perman_complex_fock_minors: the same arguments, checks, randomness, pmf
+ * stage and stats, except that visited_steps is the sum over the stages of
+ * that entry's (gray_steps stays the nominal nsamples sum_k 2^(k-2)) and
+ * est_ops_per_step = 16n - 20.  The weights differ from sup_boson_sample's in
+ * their last bits only, so a draw can differ only where u sum(w) lies within
+ * rounding of a running sum.  The device and the host twin draw identical
+ * samples, and sample s depends on (U, inputs, seed, s) only. */
+int sup_boson_sample_fock(const double* U, int M, const int32_t* inputs, int n, uint64_t nsamples, uint64_t seed,
+                          const sup_opts* o, int on_cpu, int32_t* out /* nsamples x n, ascending modes */,
+                          sup_stats* st);
 
 /* Nijenhuis-Wilf prologue (gpu_exact_dense.cu:642-652): x0[j] = a[j][n-1] - rowsum_j/2,
  * p0 = prod x0.  Host-only helper, exported for the test harness. */

@@ -20,7 +20,8 @@ from ._lib import (KERNEL_DENSE, KERNEL_SKIPPER, KERNEL_SPARYSER, LEAF_FN, SCHED
                    SCHED_STATIC, SupApproxResult, SupError, SupOpts, SupReduceOpts, SupStats)
 
 __all__ = [
-    "perman", "perman_cpu", "perman_exact", "perman_exact_range", "perman_quad", "perman_quad_range", "perman_complex", "perman_complex_range", "perman_complex_batch", "perman_complex_submatrices", "perman_complex_fock", "perman_complex_fock_plan", "perman_complex_minors", "perman_complex_minors_submatrices", "perman_complex_minors_range", "boson_sample", "read_mtx_complex", "partial", "perman_shard", "plan_info", "plan_census", "CENSUS_CLASSES", "plan_key", "prepare", "read_matrix", "read_mtx", "sort_order",
+    "perman", "perman_cpu", "perman_exact", "perman_exact_range", "perman_quad", "perman_quad_range", "perman_complex", "perman_complex_range", "perman_complex_batch", "perman_complex_submatrices", "perman_complex_fock", "perman_complex_fock_plan", "perman_complex_fock_minors", "perman_complex_fock_minors_submatrices",
+           "perman_complex_fock_minors_plan", "perman_complex_minors", "perman_complex_minors_submatrices", "perman_complex_minors_range", "boson_sample", "read_mtx_complex", "partial", "perman_shard", "plan_info", "plan_census", "CENSUS_CLASSES", "plan_key", "prepare", "read_matrix", "read_mtx", "sort_order",
     "skip_order", "compress", "decompose", "perman_reduced", "approx", "grid_graph", "ALGOS_APPROX",
     "nw_start", "device_count", "rccl_devices", "layout", "ShardCall", "SupError", "ALGOS_DENSE", "ALGOS_SPARSE",
     "gpu_perman64_xshared_coalescing_mshared",
@@ -442,13 +443,17 @@ def perman_complex_minors_range(B, c0: int, c1: int, cpu: bool = False, threads:
 
 
 def boson_sample(U, inputs, nsamples: int, seed: int = 0, gpu_num: int = 1, device_id: int = 0, cpu: bool = False,
-                 threads: int = 16, walk_log2: int = 0, return_stats: bool = False):
+                 threads: int = 16, walk_log2: int = 0, return_stats: bool = False, collision_aware: bool = False):
     """``nsamples`` exact boson-sampling outcomes (Clifford & Clifford 2018,
     algorithm A; sup_boson_sample): n = len(inputs) photons enter the M x M
     unitary U in the distinct modes ``inputs``.  np.ndarray int32 of shape
     [nsamples, n]: each row the output modes, ascending (a mode repeats where
     photons collide).  Sample s depends on (U, inputs, seed, s) only — the
-    GPU and (cpu=True) the host twin draw identical samples."""
+    GPU and (cpu=True) the host twin draw identical samples.
+    ``collision_aware=True`` (sup_boson_sample_fock) takes every stage's
+    minors from ``perman_complex_fock_minors_submatrices``, whose walk
+    collapses the modes drawn more than once; its stats' ``visited_steps`` is
+    the sum of the terms walked, ``gray_steps`` stays nominal."""
     u = np.ascontiguousarray(np.asarray(U, dtype=np.complex128))
     if u.ndim != 2 or u.shape[0] != u.shape[1] or u.shape[0] < 1:
         raise ValueError(f"expected a square matrix U, got shape {u.shape}")
@@ -466,9 +471,9 @@ def boson_sample(U, inputs, nsamples: int, seed: int = 0, gpu_num: int = 1, devi
     lib = _lib.load()
     o = _opts(gpu_num=gpu_num, device_id=device_id, threads=threads, walk_log2=walk_log2)
     out, st = np.zeros((max(nsamples, 1), n), np.int32), SupStats()
-    _lib.check(lib.sup_boson_sample(u.ctypes.data, u.shape[0], i32.ctypes.data, n, nsamples,
-                                    int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(o), int(bool(cpu)), out.ctypes.data,
-                                    C.byref(st)), "boson_sample")
+    entry = lib.sup_boson_sample_fock if collision_aware else lib.sup_boson_sample
+    _lib.check(entry(u.ctypes.data, u.shape[0], i32.ctypes.data, n, nsamples, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                     C.byref(o), int(bool(cpu)), out.ctypes.data, C.byref(st)), "boson_sample")
     v = out[:nsamples].copy()
     if not return_stats:
         return v
@@ -539,6 +544,71 @@ def perman_complex_fock_plan(rows, cols):
     if single:
         return int(terms[0]), int(side[0])
     return terms[:count].copy(), side[:count].copy()
+
+
+def perman_complex_fock_minors_submatrices(U, rows, cols, gpu_num: int = 1, device_id: int = 0, cpu: bool = False,
+                                           threads: int = 16, return_stats: bool = False):
+    """``perman_complex_minors_submatrices`` with the repeated columns
+    collapsed (sup_perman_complex_fock_minors): ``rows`` of shape [count, n],
+    ``cols`` of shape [count, n-1], result [k, j] the permanent of
+    ``U[np.ix_(rows[k], cols[k])]`` without row j, all n from one walk over the
+    column multiplicities, T = prod (t'_k + 1) states instead of 2^(n-2)
+    (walk_cplxfm.hip, or (cpu=True) its host twin, bit-identical).  n <= 32.
+    The values equal ``perman_complex_minors_submatrices``' up to rounding,
+    not bit for bit."""
+    u = np.ascontiguousarray(np.asarray(U, dtype=np.complex128))
+    if u.ndim != 2 or u.shape[0] < 1 or u.shape[1] < 1:
+        raise ValueError(f"expected a non-empty 2-d matrix U, got shape {u.shape}")
+    r = np.asarray(rows)
+    if r.ndim != 2 or r.shape[1] < 1:
+        raise ValueError(f"rows must have shape [count, n], got {r.shape}")
+    count, n = r.shape
+    c = np.asarray(cols)
+    if c.shape != (count, n - 1):
+        raise ValueError(f"cols must have shape [count, n - 1] = {(count, n - 1)}, got {c.shape}")
+    r32 = _index_array("rows", r, n)
+    c32 = _index_array("cols", c.reshape(count, n - 1), n - 1)
+    lib = _lib.load()
+    o = _opts(gpu_num=gpu_num, device_id=device_id, threads=threads)
+    out, st = np.zeros(2 * max(count * n, 1)), SupStats()
+    _lib.check(lib.sup_perman_complex_fock_minors(u.ctypes.data, u.shape[0], u.shape[1], r32.ctypes.data,
+                                                  c32.ctypes.data, n, count, C.byref(o), int(bool(cpu)),
+                                                  out.ctypes.data, C.byref(st)),
+               "perman_complex_fock_minors_submatrices")
+    v = _batch_result(out, count * n).reshape(count, n)
+    return (v, st.as_dict()) if return_stats else v
+
+
+def perman_complex_fock_minors(B, gpu_num: int = 1, device_id: int = 0, cpu: bool = False, threads: int = 16,
+                               return_stats: bool = False):
+    """The permanents of the n minors of one n x (n-1) complex matrix B through
+    ``perman_complex_fock_minors_submatrices`` with identity lists (no column
+    repeats, so T = 2^(n-2)).  np.ndarray complex128 of shape [n]."""
+    b, n = _minors_mat(B)
+    u = b if n > 1 else np.zeros((1, 1), np.complex128)
+    rows = np.arange(n, dtype=np.int32)[None, :]
+    cols = np.arange(n - 1, dtype=np.int32)[None, :]
+    res = perman_complex_fock_minors_submatrices(u, rows, cols, gpu_num=gpu_num, device_id=device_id, cpu=cpu,
+                                                 threads=threads, return_stats=return_stats)
+    return (res[0][0], res[1]) if return_stats else res[0]
+
+
+def perman_complex_fock_minors_plan(cols):
+    """The terms T ``perman_complex_fock_minors_submatrices`` walks for these
+    column lists (sup_perman_complex_fock_minors_plan, host only): an int for a
+    list of shape [n-1], a uint64 array of shape [count] for [count, n-1]."""
+    c = np.asarray(cols)
+    single = c.ndim == 1
+    if single:
+        c = c[None, :]
+    if c.ndim != 2:
+        raise ValueError(f"cols must have shape [n - 1] or [count, n - 1], got {np.shape(cols)}")
+    count, q = c.shape
+    c32 = _index_array("cols", c, q)
+    terms = np.zeros(max(count, 1), np.uint64)
+    _lib.check(_lib.load().sup_perman_complex_fock_minors_plan(c32.ctypes.data, q + 1, count, terms.ctypes.data),
+               "perman_complex_fock_minors_plan")
+    return int(terms[0]) if single else terms[:count].copy()
 
 
 def partial(mat, start: int, end: int, kernel: str = "dense", gpu_num: int = 1, device_id: int = 0,

@@ -40,6 +40,7 @@ EXPORTS = [
     "sup_perman_complex_batch", "sup_perman_complex_submatrices",
     "sup_perman_complex_fock", "sup_perman_complex_fock_plan",
     "sup_perman_complex_minors", "sup_perman_complex_minors_range", "sup_boson_sample",
+    "sup_perman_complex_fock_minors", "sup_perman_complex_fock_minors_plan", "sup_boson_sample_fock",
     "sup_gpu_perman64_xshared_coalescing_mshared",
     "sup_gpu_perman64_xshared_coalescing_mshared_multigpu",
     "sup_gpu_perman64_xshared_coalescing_mshared_multigpucpu_chunks",
@@ -134,7 +135,7 @@ def load() -> C.CDLL:
             build()
         lib = C.CDLL(LIB_PATH)
         _declare(lib)
-        if lib.sup_abi_version() != 16:
+        if lib.sup_abi_version() != 17:
             raise RuntimeError("libsuperman_hip.so ABI version mismatch")
         _lib = lib
         return lib
@@ -177,6 +178,11 @@ def _declare(lib: C.CDLL) -> None:
                                                     C.POINTER(SupStats)]
     lib.sup_boson_sample.argtypes = [P, I, P, I, C.c_uint64, C.c_uint64, C.POINTER(SupOpts), I, P,
                                      C.POINTER(SupStats)]
+    lib.sup_perman_complex_fock_minors.argtypes = [P, I, I, P, P, I, C.c_uint64, C.POINTER(SupOpts), I, P,
+                                                   C.POINTER(SupStats)]
+    lib.sup_perman_complex_fock_minors_plan.argtypes = [P, I, C.c_uint64, P]
+    lib.sup_boson_sample_fock.argtypes = [P, I, P, I, C.c_uint64, C.c_uint64, C.POINTER(SupOpts), I, P,
+                                          C.POINTER(SupStats)]
     lib.sup_read_mtx_complex.argtypes = [C.c_char_p, C.POINTER(P), C.POINTER(I), C.POINTER(I)]
     lib.sup_perman_shard.argtypes = [P, I, I, I, I, I, C.POINTER(SupOpts), C.POINTER(D), C.POINTER(SupStats)]
     lib.sup_plan_info.argtypes = [P, I, I, I, C.POINTER(SupOpts), C.POINTER(I), P, C.POINTER(I), C.POINTER(I),

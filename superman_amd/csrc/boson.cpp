@@ -30,6 +30,12 @@
 // rounding leaves none, the last i with w_i > 0.  The minors are bit-identical
 // on the device and the host twin, so both draw identical samples, and sample
 // s depends on (U, inputs, seed, s) only.
+//
+// sup_boson_sample_fock is the same function with one switch: every stage's
+// minors come from cplx_fock_minors (cplx_fock_minors.cpp), whose
+// walk collapses the repeated modes among the k - 1 drawn so far.  Its minors
+// differ from cplx_minors' in their last bits, so a draw can differ where
+// u tot lies within rounding of a running sum; everything else is shared.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -64,8 +70,8 @@ void parallel_ranges(uint64_t count, int T, const Fn& fn) {
 }  // namespace
 
 int boson_sample(const double* U, int M, const int32_t* inputs, int n, uint64_t nsamples, uint64_t seed,
-                 const sup_opts& o, bool on_cpu, int32_t* out, BosonInfo* info) {
-  const char* who = "sup_boson_sample";
+                 const sup_opts& o, bool on_cpu, int32_t* out, BosonInfo* info, bool collision_aware) {
+  const char* who = collision_aware ? "sup_boson_sample_fock" : "sup_boson_sample";
   if (!U || !inputs || !out) {
     set_error(std::string(who) + ": null pointer");
     return SUP_EINVAL;
@@ -156,12 +162,18 @@ int boson_sample(const double* U, int M, const int32_t* inputs, int n, uint64_t 
       CplxBatchIn in;
       in.U = Ut.data(), in.R = M, in.C = M, in.rows = rows.data(), in.cols = cols.data();
       CplxInfo ci;
+      FockInfo fi;
       const auto t0 = std::chrono::steady_clock::now();
-      if (int rc = cplx_minors(in, k, nsamples, o, on_cpu, minors.data(), &ci)) return rc;
+      // the stage's minors: the one walk over all Gray states, or (collision_aware)
+      // the walk over the multiplicities of the modes drawn so far
+      if (int rc = collision_aware ? cplx_fock_minors(in, k, nsamples, o, on_cpu, minors.data(), &fi)
+                                   : cplx_minors(in, k, nsamples, o, on_cpu, minors.data(), &ci))
+        return rc;
       const auto t1 = std::chrono::steady_clock::now();
-      bi.kernel_ms += ci.kernel_ms;
-      bi.devices = std::max(bi.devices, ci.devices);
+      bi.kernel_ms += collision_aware ? fi.kernel_ms : ci.kernel_ms;
+      bi.devices = std::max(bi.devices, collision_aware ? fi.devices : ci.devices);
       if (k >= 2) bi.steps += nsamples << std::max(k - 2, 0);
+      if (k >= 2) bi.visited += collision_aware ? fi.terms : nsamples << std::max(k - 2, 0);
       parallel_ranges(nsamples, T, [&](uint64_t s0, uint64_t s1) {
         std::vector<double> w(M);
         for (uint64_t s = s0; s < s1; ++s) {

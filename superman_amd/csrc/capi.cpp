@@ -567,28 +567,72 @@ int sup_perman_complex_minors_range(const double* mat, int n, uint64_t c0, uint6
   return SUP_OK;
 }
 
-int sup_boson_sample(const double* U, int M, const int32_t* inputs, int n, uint64_t nsamples, uint64_t seed,
-                     const sup_opts* o_in, int on_cpu, int32_t* out, sup_stats* st) {
+int sup_perman_complex_fock_minors(const double* U, int R, int C, const int32_t* rows, const int32_t* cols, int n,
+                                   uint64_t count, const sup_opts* o_in, int on_cpu, double* out, sup_stats* st) {
+  auto t0 = std::chrono::steady_clock::now();
+  if (!U || !rows || (!cols && n != 1) || !out) {
+    set_error("sup_perman_complex_fock_minors: null matrix, index list or output pointer");
+    return SUP_EINVAL;
+  }
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  CplxBatchIn in;
+  in.U = U, in.R = R, in.C = C, in.rows = rows, in.cols = cols;
+  FockInfo fi;
+  if (int rc = cplx_fock_minors(in, n, count, o, on_cpu != 0, out, &fi)) return rc;
+  if (st) {
+    std::memset(st, 0, sizeof(*st));
+    st->kernel_ms = fi.kernel_ms;
+    st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    st->gray_steps = n <= 1 ? 0 : count << (n - 2);  // nominal: the one walk over every Gray state
+    st->visited_steps = fi.terms;
+    st->devices_used = fi.devices;
+    st->grid = fi.grid;
+    st->walk_kind = (int)kWalkDense;
+    st->leaves = (int)std::min<uint64_t>(count * (uint64_t)n, 0x7fffffffu);
+    st->est_ops_per_step = std::max(16.0 * n - 20.0, 0.0);
+  }
+  return SUP_OK;
+}
+
+int sup_perman_complex_fock_minors_plan(const int32_t* cols, int n, uint64_t count, uint64_t* terms) {
+  return cplx_fock_minors_plan(cols, n, count, terms);
+}
+
+// Both samplers: collision_aware picks the per-stage minors entry.
+static int boson_sample_entry(const double* U, int M, const int32_t* inputs, int n, uint64_t nsamples, uint64_t seed,
+                              const sup_opts* o_in, int on_cpu, int32_t* out, sup_stats* st, bool collision_aware) {
   auto t0 = std::chrono::steady_clock::now();
   sup_opts o;
   if (o_in) o = *o_in;
   else sup_opts_init(&o);
   BosonInfo bi;
-  if (int rc = boson_sample(U, M, inputs, n, nsamples, seed, o, on_cpu != 0, out, &bi)) return rc;
+  if (int rc = boson_sample(U, M, inputs, n, nsamples, seed, o, on_cpu != 0, out, &bi, collision_aware)) return rc;
   if (st) {
     std::memset(st, 0, sizeof(*st));
     st->kernel_ms = bi.kernel_ms;
     st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     st->gray_steps = bi.steps;
-    st->visited_steps = bi.steps;
+    st->visited_steps = bi.visited;
     st->devices_used = bi.devices;
     st->walk_kind = (int)kWalkDense;
     st->leaves = (int)std::min<uint64_t>(nsamples, 0x7fffffffu);
-    st->est_ops_per_step = std::max(16.0 * n - 24.0, 0.0);
+    st->est_ops_per_step = std::max(16.0 * n - (collision_aware ? 20.0 : 24.0), 0.0);
     st->partials[0] = bi.minors_ms;  // wall time inside the minors calls
     st->partials[1] = bi.pmf_ms;     // wall time of the host pmf and draw stage
   }
   return SUP_OK;
+}
+
+int sup_boson_sample(const double* U, int M, const int32_t* inputs, int n, uint64_t nsamples, uint64_t seed,
+                     const sup_opts* o_in, int on_cpu, int32_t* out, sup_stats* st) {
+  return boson_sample_entry(U, M, inputs, n, nsamples, seed, o_in, on_cpu, out, st, false);
+}
+
+int sup_boson_sample_fock(const double* U, int M, const int32_t* inputs, int n, uint64_t nsamples, uint64_t seed,
+                          const sup_opts* o_in, int on_cpu, int32_t* out, sup_stats* st) {
+  return boson_sample_entry(U, M, inputs, n, nsamples, seed, o_in, on_cpu, out, st, true);
 }
 
 int sup_perman_reduced_exact(const void* mat, sup_dtype t, int n, const sup_opts* o_in, int on_cpu,

@@ -31,6 +31,7 @@
 #include <string>
 #include <thread>
 
+#include "cplx_fock_build.hpp"
 #include "cx.hpp"
 #include "engine.hpp"
 
@@ -40,75 +41,19 @@ namespace {
 
 constexpr size_t kFockSlabCapBytes = (size_t)256 << 20;
 
-// Fixed-size (n <= 64) so that planning a matrix allocates nothing: a call
-// plans 10^4..10^7 of them.
-struct Groups {
-  int K = 0;
-  int32_t val[SUP_MAX_N];  // distinct indices, order of first appearance
-  int mult[SUP_MAX_N];
-};
-
-Groups group_of(const int32_t* idx, int n) {
-  Groups g;
-  for (int j = 0; j < n; ++j) {
-    int k = 0;
-    while (k < g.K && g.val[k] != idx[j]) ++k;
-    if (k == g.K) {
-      g.val[k] = idx[j];
-      g.mult[k] = 0;
-      ++g.K;
-    }
-    ++g.mult[k];
-  }
-  return g;
-}
-
-struct FockLayout {
-  int nd = 0;                  // digits: the groups with t' >= 1, lowest first
-  uint32_t radix[SUP_MAX_N];
-  int col[SUP_MAX_N];          // the group of each digit
-  int nwalk = 0;               // walk digits: digits [0, nwalk)
-  uint32_t Tw = 1;
-  uint64_t H = 1, T = 1;
-};
-
-FockLayout fock_layout(const Groups& g) {
-  FockLayout l;
-  int held = 0;
-  for (int k = 1; k < g.K; ++k)
-    if (g.mult[k] < g.mult[held]) held = k;
-  for (int k = 0; k < g.K; ++k) {
-    const int tp = g.mult[k] - (k == held ? 1 : 0);
-    if (tp < 1) continue;
-    l.radix[l.nd] = (uint32_t)tp + 1u;
-    l.col[l.nd] = k;
-    ++l.nd;
-    l.T *= (uint64_t)tp + 1u;  // <= 2^(n-1) <= 2^63
-  }
-  l.H = l.T;
-  for (int d = 0; d < l.nd; ++d) {
-    const uint32_t r = l.radix[d];
-    if ((uint64_t)l.Tw * r > kFockWalkMax || l.H / r < 64) break;
-    l.Tw *= r;
-    l.H /= r;
-    l.nwalk = d + 1;
-  }
-  return l;
-}
-
 // The side collapsed for one matrix and that side's groups and layout.
 struct FockChoice {
   int side = 0;
-  Groups g;
+  FockGroups g;
   FockLayout lay;
 };
 
 FockChoice fock_choose(const int32_t* rows, const int32_t* cols, int n) {
   FockChoice c, r;
-  c.g = group_of(cols, n);
+  c.g = fock_group_of(cols, n);
   c.lay = fock_layout(c.g);
   r.side = 1;
-  r.g = group_of(rows, n);
+  r.g = fock_group_of(rows, n);
   r.lay = fock_layout(r.g);
   return r.lay.T < c.lay.T ? r : c;
 }
@@ -138,11 +83,8 @@ size_t fock_bytes(int n, const FockChoice& c) {
 // by walk-digit list.  host_tables: write the table and x(0) here (the host
 // twin); the device path leaves that to cplx_fock_prepare, which reads the
 // groups recorded in S.grp.
-void fock_append(FockSlab& S, const CplxBatchIn& in, int n, uint64_t k, const FockChoice& c,
-                 std::map<std::vector<uint32_t>, uint32_t>& progs, bool host_tables) {
-  const int NP = pad8(n), K = c.g.K;
-  const std::vector<double>& wts = fock_weights();
-  const FockLayout& l = c.lay;
+void fock_append(FockSlab& S, const CplxBatchIn& in, int n, uint64_t k, const FockChoice& c, FockProgs& progs,
+                 bool host_tables) {
   const int32_t* rows = in.rows + k * n;
   const int32_t* cols = in.cols + k * n;
   // b_k[j] as its (re, im) pair: columns collapsed, b_k[j] = U[rows[j]][val_k];
@@ -151,84 +93,7 @@ void fock_append(FockSlab& S, const CplxBatchIn& in, int n, uint64_t k, const Fo
     return c.side == 0 ? in.U + 2 * ((size_t)rows[j] * in.C + (size_t)c.g.val[kk])
                        : in.U + 2 * ((size_t)c.g.val[kk] * in.C + (size_t)cols[j]);
   };
-  FockMat M{};
-  M.tab = S.tab_doubles;
-  M.x0 = S.x0_doubles;
-  M.im_off = (uint32_t)(2 * K * NP * 8);
-  M.K = (uint32_t)K;
-  M.side = (uint32_t)c.side;
-  M.grp = (uint32_t)S.grp.size();
-  for (int kk = 0; kk < K; ++kk) S.grp.push_back(c.g.val[kk]), S.grp.push_back(c.g.mult[kk]);
-  const size_t plane = (size_t)2 * K * NP;
-  S.tab_doubles += 2 * plane;
-  S.x0_doubles += 2 * (size_t)NP;
-  if (host_tables) {
-    S.tabs.resize(S.tab_doubles, 0.0);
-    S.x0s.resize(S.x0_doubles, 0.0);
-    double* t = S.tabs.data() + M.tab;
-    double* x0 = S.x0s.data() + M.x0;
-    for (int kk = 0; kk < K; ++kk)
-      for (int j = 0; j < n; ++j) {
-        const double* v = at(kk, j);
-        t[(size_t)(2 * kk) * NP + j] = v[0];
-        t[(size_t)(2 * kk + 1) * NP + j] = -v[0];
-        t[plane + (size_t)(2 * kk) * NP + j] = v[1];
-        t[plane + (size_t)(2 * kk + 1) * NP + j] = -v[1];
-      }
-    // x(0)_j = 1/2 sum_k t_k b_k[j]: s = fma(t_k, b, s) for k ascending, then s / 2
-    for (int j = 0; j < n; ++j) {
-      double sr = 0.0, si = 0.0;
-      for (int kk = 0; kk < K; ++kk) {
-        const double* v = at(kk, j);
-        sr = __builtin_fma((double)c.g.mult[kk], v[0], sr);
-        si = __builtin_fma((double)c.g.mult[kk], v[1], si);
-      }
-      x0[j] = 0.5 * sr;
-      x0[NP + j] = 0.5 * si;
-    }
-  }
-  // the step program of the walk digits (shared by every matrix of the slab with this list)
-  static thread_local std::vector<uint32_t> key;  // reused: no allocation per matrix
-  key.clear();
-  for (int d = 0; d < l.nwalk; ++d) key.push_back(l.radix[d]), key.push_back((uint32_t)l.col[d]);
-  auto it = progs.find(key);
-  if (it == progs.end()) {
-    const uint32_t base = (uint32_t)S.prog.size();
-    std::vector<uint32_t> g(l.nwalk, 0), prev(l.nwalk, 0);
-    for (uint32_t tt = 0; tt < l.Tw; ++tt) {
-      // reflected mixed-radix Gray code of tt: digit i runs down where the
-      // number formed by the digits above it is odd
-      uint32_t q = tt;
-      double w = 1.0;
-      for (int i = 0; i < l.nwalk; ++i) {
-        const uint32_t r = l.radix[i], a = q % r;
-        q /= r;
-        g[i] = (q & 1u) ? r - 1u - a : a;
-        w = w * wts[wt_row((int)r - 1) + g[i]];
-      }
-      FockStep s{0u, 0u, w};
-      if (tt > 0)
-        for (int i = 0; i < l.nwalk; ++i)
-          if (g[i] != prev[i])  // v up: x -= b (the -b row), v down: x += b
-            s.off = (uint32_t)((2 * l.col[i] + (g[i] > prev[i] ? 1 : 0)) * NP * 8);
-      S.prog.push_back(s);
-      prev = g;
-    }
-    S.prog.push_back(FockStep{0u, 0u, 0.0});  // padding: the walk asks for entry t + 1 ahead
-    it = progs.emplace(key, base).first;
-  }
-  M.prog = it->second;
-  M.Tw = l.Tw;
-  M.dig = (uint32_t)S.dig.size();
-  M.ndig = (uint32_t)(l.nd - l.nwalk);
-  for (int d = l.nwalk; d < l.nd; ++d)
-    S.dig.push_back(FockDigit{l.radix[d], (uint32_t)(2 * l.col[d] * NP * 8), wt_row((int)l.radix[d] - 1), 0u});
-  M.H = (uint32_t)l.H;
-  M.chunk0 = (uint32_t)S.chunks.size();
-  M.chunks = (uint32_t)((l.H + 63) / 64);
-  const uint32_t mi = (uint32_t)S.mats.size();
-  for (uint32_t cidx = 0; cidx < M.chunks; ++cidx) S.chunks.push_back(FockChunk{mi, cidx});
-  S.mats.push_back(M);
+  fock_append_mat(S, n, c.g, c.lay, c.side, progs, host_tables, at);
 }
 
 // One wave-chunk of the slab's queue, every lane, then the 64-lane xor
@@ -304,17 +169,6 @@ void fock_cpu(const FockSlab& S, int threads, double* out) {
   }
 }
 
-// fn(a, b) on `threads` contiguous parts of [0, count).
-template <class F>
-void fock_parallel(uint64_t count, int threads, F fn) {
-  const int nt = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::max(threads, 1), count / 256 + 1));
-  std::vector<std::thread> th;
-  for (int w = 1; w < nt; ++w)
-    th.emplace_back([&, w]() { fn(count * (uint64_t)w / (uint64_t)nt, count * (uint64_t)(w + 1) / (uint64_t)nt); });
-  fn(0, count / (uint64_t)nt);
-  for (auto& t : th) t.join();
-}
-
 int check_lists(const char* who, int R, int C, const int32_t* rows, const int32_t* cols, int n, uint64_t count) {
   for (uint64_t k = 0; k < count; ++k)
     for (int j = 0; j < n; ++j) {
@@ -331,6 +185,96 @@ int check_lists(const char* who, int R, int C, const int32_t* rows, const int32_
 }
 
 }  // namespace
+
+FockGroups fock_group_of(const int32_t* idx, int n) {
+  FockGroups g;
+  for (int j = 0; j < n; ++j) {
+    int k = 0;
+    while (k < g.K && g.val[k] != idx[j]) ++k;
+    if (k == g.K) {
+      g.val[k] = idx[j];
+      g.mult[k] = 0;
+      ++g.K;
+    }
+    ++g.mult[k];
+  }
+  return g;
+}
+
+FockLayout fock_layout(const FockGroups& g) {
+  FockLayout l;
+  int held = 0;
+  for (int k = 1; k < g.K; ++k)
+    if (g.mult[k] < g.mult[held]) held = k;
+  for (int k = 0; k < g.K; ++k) {
+    const int tp = g.mult[k] - (k == held ? 1 : 0);
+    if (tp < 1) continue;
+    l.radix[l.nd] = (uint32_t)tp + 1u;
+    l.col[l.nd] = k;
+    ++l.nd;
+    l.T *= (uint64_t)tp + 1u;  // <= 2^(n-1) <= 2^63
+  }
+  l.H = l.T;
+  for (int d = 0; d < l.nd; ++d) {
+    const uint32_t r = l.radix[d];
+    if ((uint64_t)l.Tw * r > kFockWalkMax || l.H / r < 64) break;
+    l.Tw *= r;
+    l.H /= r;
+    l.nwalk = d + 1;
+  }
+  return l;
+}
+
+void fock_append_desc(FockSlab& S, FockMat M, int n, const FockLayout& l, FockProgs& progs) {
+  const int NP = pad8(n);
+  const std::vector<double>& wts = fock_weights();
+  // the step program of the walk digits (shared by every matrix of the slab with this list)
+  static thread_local std::vector<uint32_t> key;  // reused: no allocation per matrix
+  key.clear();
+  for (int d = 0; d < l.nwalk; ++d) key.push_back(l.radix[d]), key.push_back((uint32_t)l.col[d]);
+  auto it = progs.find(key);
+  if (it == progs.end()) {
+    const uint32_t base = (uint32_t)S.prog.size();
+    // reflected mixed-radix Gray code of tt: a = the digits of tt, digit i
+    // runs down (g = radix - 1 - a) where the number formed by the digits
+    // above it is odd.  tt is counted up digit by digit (a slab of sampler
+    // stages builds hundreds of programs: no division per digit and step).
+    uint32_t a[SUP_MAX_N] = {0}, g[SUP_MAX_N] = {0};
+    bool odd[SUP_MAX_N] = {false};
+    for (uint32_t tt = 0; tt < l.Tw; ++tt) {
+      FockStep s{0u, 0u, 1.0};
+      if (tt > 0) {
+        // digits below c wrap (the number above each of them grows by one, and
+        // their reflected value stays), digit c steps: the one g that changes
+        int c = 0;
+        while (a[c] == l.radix[c] - 1u) a[c] = 0, odd[c] = !odd[c], ++c;
+        ++a[c];
+        for (int i = 0; i <= c; ++i) {
+          const uint32_t v = odd[i] ? l.radix[i] - 1u - a[i] : a[i];
+          if (v != g[i])  // v up: x -= b (the -b row), v down: x += b
+            s.off = (uint32_t)((2 * l.col[i] + (v > g[i] ? 1 : 0)) * NP * 8);
+          g[i] = v;
+        }
+      }
+      for (int i = 0; i < l.nwalk; ++i) s.w = s.w * wts[wt_row((int)l.radix[i] - 1) + g[i]];
+      S.prog.push_back(s);
+    }
+    S.prog.push_back(FockStep{0u, 0u, 0.0});  // padding: the walk asks for entry t + 1 ahead
+    it = progs.emplace(key, base).first;
+  }
+  M.prog = it->second;
+  M.Tw = l.Tw;
+  M.dig = (uint32_t)S.dig.size();
+  M.ndig = (uint32_t)(l.nd - l.nwalk);
+  for (int d = l.nwalk; d < l.nd; ++d)
+    S.dig.push_back(FockDigit{l.radix[d], (uint32_t)(2 * l.col[d] * NP * 8), wt_row((int)l.radix[d] - 1), 0u});
+  M.H = (uint32_t)l.H;
+  M.chunk0 = (uint32_t)S.chunks.size();
+  M.chunks = (uint32_t)((l.H + 63) / 64);
+  const uint32_t mi = (uint32_t)S.mats.size();
+  for (uint32_t cidx = 0; cidx < M.chunks; ++cidx) S.chunks.push_back(FockChunk{mi, cidx});
+  S.mats.push_back(M);
+}
 
 const std::vector<double>& fock_weights() {
   static const std::vector<double> w = [] {
@@ -447,7 +391,7 @@ int cplx_perman_fock(const CplxBatchIn& in, int n, uint64_t count, const sup_opt
         FockSlab S;
         S.n = n;
         S.first = k;
-        std::map<std::vector<uint32_t>, uint32_t> progs;
+        FockProgs progs;
         size_t bytes = 0;
         const uint64_t k0 = k;
         bool full = false;

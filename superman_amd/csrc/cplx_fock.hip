@@ -14,6 +14,10 @@
 // cplx_fock_fold: one thread per matrix runs fock_fold (cplx_fock.hpp, the
 // host twin's own function) over the matrix's chunk partials and writes
 // 2 x the sum: per(A) = 2 sum, a power-of-two scale, exact.
+//
+// The collision-aware one-walk minors (walk_cplxfm.hip) use the
+// same prepare (side 0, tables of n rows) and a fold over n outputs per
+// matrix, cplx_fock_minors_fold; their N-range dispatch is here too.
 #include "cplx_fock.hpp"
 #include "cx.hpp"
 #include "kernels.hpp"
@@ -106,6 +110,41 @@ hipError_t cplx_fock_occupancy(int n, int* blocks_per_cu) {
          : n <= 32 ? occupancy_cplxf_17(n, blocks_per_cu)
          : n <= 48 ? occupancy_cplxf_33(n, blocks_per_cu)
                    : occupancy_cplxf_49(n, blocks_per_cu);
+}
+
+// cplx_fock_minors_fold: the collision-aware one-walk minors (walk_cplxfm.hip)
+// leave n outputs per matrix, output j's partials at 2 (n chunk0 + j chunks);
+// one thread per output runs fock_fold over them and writes 2 x the sum
+// (DESIGN.md §8e).
+__global__ __launch_bounds__(kBlock) void cplx_fock_minors_fold(const double* __restrict__ parts,
+                                                                const FockMat* __restrict__ mats, uint64_t K, int n,
+                                                                double* __restrict__ out) {
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= K * (uint64_t)n) return;
+  const uint64_t k = i / (uint64_t)n, j = i - k * (uint64_t)n;
+  const uint32_t chunk0 = mats[k].chunk0, chunks = mats[k].chunks;
+  const cx v = fock_fold(parts + 2 * ((uint64_t)n * chunk0 + j * chunks), chunks);
+  out[2 * i] = 2.0 * v.re;
+  out[2 * i + 1] = 2.0 * v.im;
+}
+
+hipError_t launch_cplx_fock_minors_fold(const double* parts, const FockMat* mats, uint64_t K, int n, double* out,
+                                        hipStream_t s) {
+  if (K == 0 || n < 2 || n > 32) return hipErrorInvalidValue;
+  const uint64_t blocks = (K * (uint64_t)n + kBlock - 1) / kBlock;
+  if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(cplx_fock_minors_fold, dim3((unsigned)blocks), dim3(kBlock), 0, s, parts, mats, K, n, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_cplx_fock_minors(int n, const FockParams& p, int grid, hipStream_t s) {
+  if (n < 2 || n > 32) return hipErrorInvalidValue;
+  return n <= 16 ? launch_cplxfm_1(n, p, grid, s) : launch_cplxfm_17(n, p, grid, s);
+}
+
+hipError_t cplx_fock_minors_occupancy(int n, int* blocks_per_cu) {
+  if (n < 2 || n > 32) return hipErrorInvalidValue;
+  return n <= 16 ? occupancy_cplxfm_1(n, blocks_per_cu) : occupancy_cplxfm_17(n, blocks_per_cu);
 }
 
 }  // namespace sup

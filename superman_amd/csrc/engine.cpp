@@ -1186,13 +1186,18 @@ int run_cplx_minors_range(int dev, int n, const Layout& lay, const CplxBatchIn& 
 // prepare (tables and x(0) written on the device), the walk over the slab's
 // queue and the per-matrix fold run on the context's stream with no host work
 // between them, and one download brings 16 bytes per matrix into out.
-int run_cplx_fock(int dev, const FockSlab& S, const CplxBatchIn& in, double* out, double* kernel_ms, int* grid_out) {
+// minors: the slab of the collision-aware one-walk minors (walk_cplxfm.hip):
+// tables of S.n rows from the row lists alone (the column groups are in
+// S.grp), S.n partials per wave-chunk and S.n outputs per matrix.
+static int run_cplx_fock_impl(int dev, const FockSlab& S, const CplxBatchIn& in, bool minors, double* out,
+                              double* kernel_ms, int* grid_out) {
   if (kernel_ms) *kernel_ms = 0.0;
   if (grid_out) *grid_out = 0;
   const uint64_t K = S.mats.size(), chunks = S.chunks.size();
   if (K == 0) return SUP_OK;
-  if (S.n < 1 || S.n > SUP_MAX_N || chunks == 0 || chunks > 0x7fffffffull || !out || !in.U || !in.rows || !in.cols ||
-      in.R < 1 || in.C < 1) {
+  const uint64_t outs = minors ? (uint64_t)S.n : 1;  // partials per chunk, results per matrix
+  if (S.n < (minors ? 2 : 1) || S.n > (minors ? 32 : SUP_MAX_N) || chunks == 0 || chunks * outs > 0x7fffffffull || !out ||
+      !in.U || !in.rows || (!minors && !in.cols) || in.R < 1 || in.C < 1) {
     set_error("run_cplx_fock: bad request");
     return SUP_EINVAL;
   }
@@ -1211,12 +1216,12 @@ int run_cplx_fock(int dev, const FockSlab& S, const CplxBatchIn& in, double* out
   if (rc) return rc;
   DeviceCtx* c = guard.c;
   int occ = 0;
-  SUP_HIP(cplx_fock_occupancy(S.n, &occ));
+  SUP_HIP(minors ? cplx_fock_minors_occupancy(S.n, &occ) : cplx_fock_occupancy(S.n, &occ));
   if ((rc = ensure(c->d_cbtab, c->cbtab_cap, (size_t)(S.tab_doubles + S.x0_doubles)))) return rc;
   if ((rc = ensure(c->d_cbidx, c->cbidx_cap, (size_t)K * 2 * n))) return rc;
   if ((rc = ensure(c->d_cbU, c->cbU_cap, (size_t)2 * in.R * in.C))) return rc;
-  if ((rc = ensure(c->d_chunk, c->chunk_cap, (size_t)(2 * chunks)))) return rc;
-  if ((rc = ensure(c->d_cbout, c->cbout_cap, (size_t)K * 2))) return rc;
+  if ((rc = ensure(c->d_chunk, c->chunk_cap, (size_t)(2 * chunks * outs)))) return rc;
+  if ((rc = ensure(c->d_cbout, c->cbout_cap, (size_t)(K * outs * 2)))) return rc;
   if ((rc = ensure(c->d_fock, c->fock_cap, u_end))) return rc;
   hipStream_t s = c->stream;
   c->tables_uid = 0;  // the walk leaves head 0 nonzero
@@ -1224,13 +1229,14 @@ int run_cplx_fock(int dev, const FockSlab& S, const CplxBatchIn& in, double* out
   double* d_tabs = c->d_cbtab;
   double* d_x0s = c->d_cbtab + S.tab_doubles;
   int32_t* d_rows = c->d_cbidx;
-  int32_t* d_cols = c->d_cbidx + (size_t)K * n;
+  // the minors' prepare has side 0 everywhere: it reads the row lists and S.grp, never the column lists
+  int32_t* d_cols = minors ? d_rows : c->d_cbidx + (size_t)K * n;
   auto up = [&](void* dst, const void* src, size_t bytes) {
     return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
   };
   SUP_HIP(up(c->d_cbU, in.U, (size_t)2 * in.R * in.C * sizeof(double)));
   SUP_HIP(up(d_rows, in.rows + S.first * n, (size_t)K * n * sizeof(int32_t)));
-  SUP_HIP(up(d_cols, in.cols + S.first * n, (size_t)K * n * sizeof(int32_t)));
+  if (!minors) SUP_HIP(up(d_cols, in.cols + S.first * n, (size_t)K * n * sizeof(int32_t)));
   SUP_HIP(up(c->d_fock + u_grp, S.grp.data(), S.grp.size() * sizeof(int32_t)));
   SUP_HIP(up(c->d_fock + u_prog, S.prog.data(), S.prog.size() * sizeof(FockStep)));
   SUP_HIP(up(c->d_fock + u_dig, S.dig.data(), S.dig.size() * sizeof(FockDigit)));
@@ -1257,12 +1263,28 @@ int run_cplx_fock(int dev, const FockSlab& S, const CplxBatchIn& in, double* out
   SUP_ON_DEVICE(c->dev, "collision-aware complex walk launch");
   SUP_HIP(launch_cplx_fock_prepare(c->d_cbU, in.C, d_rows, d_cols, reinterpret_cast<const int32_t*>(c->d_fock + u_grp),
                                    p.mats, S.n, K, d_tabs, d_x0s, s));
-  SUP_HIP(launch_cplx_fock(S.n, p, (int)geo.grid, s));
-  SUP_HIP(launch_cplx_fock_fold(c->d_chunk, p.mats, K, c->d_cbout, s));
+  if (minors) {
+    SUP_HIP(launch_cplx_fock_minors(S.n, p, (int)geo.grid, s));
+    SUP_HIP(launch_cplx_fock_minors_fold(c->d_chunk, p.mats, K, S.n, c->d_cbout, s));
+  } else {
+    SUP_HIP(launch_cplx_fock(S.n, p, (int)geo.grid, s));
+    SUP_HIP(launch_cplx_fock_fold(c->d_chunk, p.mats, K, c->d_cbout, s));
+  }
   SUP_HIP(hipEventRecord(c->ev1, s));
-  SUP_HIP(hipMemcpyAsync(out, c->d_cbout, (size_t)K * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+  SUP_HIP(hipMemcpyAsync(out, c->d_cbout, (size_t)(K * outs * 2) * sizeof(double), hipMemcpyDeviceToHost, s));
   if (grid_out) *grid_out = (int)geo.grid;
   return timed_sync(c, kernel_ms);
+}
+
+int run_cplx_fock(int dev, const FockSlab& S, const CplxBatchIn& in, double* out, double* kernel_ms, int* grid_out) {
+  return run_cplx_fock_impl(dev, S, in, false, out, kernel_ms, grid_out);
+}
+
+// The collision-aware one-walk minors (walk_cplxfm.hip) of slab S: the same
+// uploads, three launches and one download, 16 S.n bytes per matrix.
+int run_cplx_fock_minors(int dev, const FockSlab& S, const CplxBatchIn& in, double* out, double* kernel_ms,
+                         int* grid_out) {
+  return run_cplx_fock_impl(dev, S, in, true, out, kernel_ms, grid_out);
 }
 
 }  // namespace sup

@@ -579,10 +579,13 @@ int cplx_minors_range(const double* mat, int n, uint64_t c0, uint64_t c1, const 
 struct BosonInfo {
   double kernel_ms = 0.0, minors_ms = 0.0, pmf_ms = 0.0;
   int devices = 0;
-  uint64_t steps = 0;
+  uint64_t steps = 0, visited = 0;
 };
+// collision_aware: every stage's minors through cplx_fock_minors
+// (sup_boson_sample_fock) instead of cplx_minors; info->visited then sums the
+// stages' terms, info->steps stays the nominal count.
 int boson_sample(const double* U, int M, const int32_t* inputs, int n, uint64_t nsamples, uint64_t seed,
-                 const sup_opts& o, bool on_cpu, int32_t* out, BosonInfo* info);
+                 const sup_opts& o, bool on_cpu, int32_t* out, BosonInfo* info, bool collision_aware = false);
 
 // ---- collision-aware complex permanents (cplx_fock.cpp; walk_cplxf.hip, cplx_fock.hip) ----
 // A slab of K matrices of order n as the walk reads it (cplx_fock.hpp): the
@@ -620,5 +623,24 @@ int cplx_perman_fock(const CplxBatchIn& in, int n, uint64_t count, const sup_opt
 // Per matrix the terms T of that sum and the side collapsed (0 columns,
 // 1 rows); either output may be null.  Host only.
 int cplx_fock_plan(const int32_t* rows, const int32_t* cols, int n, uint64_t count, uint64_t* terms, int* side);
+
+// ---- collision-aware one-walk minors (cplx_fock_minors.cpp; walk_cplxfm.hip, cplx_fock.hip) ----
+// Slab S holds n x (n-1) matrices (2 <= n = S.n <= 32) with the column side
+// collapsed: tables of n rows, and n partials per wave-chunk, output j of a
+// matrix at 2 (n chunk0 + j chunks).  Prepares, walks and folds it on device
+// `dev`: out[2 (k n + j)], [.. + 1] = the permanent of its matrix k without
+// row j, bit-identical to the host twin.  in.cols is not read (the groups are
+// in S.grp).
+int run_cplx_fock_minors(int dev, const FockSlab& S, const CplxBatchIn& in, double* out, double* kernel_ms,
+                         int* grid = nullptr);
+// out[2 (k n + j)], [.. + 1] = the permanent of matrix k (entry (i, c) =
+// U[rows[k n + i]][cols[k (n-1) + c]]) without row j, k < count
+// (sup_perman_complex_fock_minors): the sum over the column multiplicity
+// vectors, all n minors from one walk.  Checks as cplx_minors', before any
+// work; n > 32 is SUP_EUNSUPPORTED.  info->terms: sum over the matrices of T.
+int cplx_fock_minors(const CplxBatchIn& in, int n, uint64_t count, const sup_opts& o, bool on_cpu, double* out,
+                     FockInfo* info);
+// Per matrix the terms T of that sum (cols: count x (n-1)).  Host only.
+int cplx_fock_minors_plan(const int32_t* cols, int n, uint64_t count, uint64_t* terms);
 
 }  // namespace sup

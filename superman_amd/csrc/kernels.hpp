@@ -100,6 +100,12 @@ SUP_DECL_CPLXF(17)
 SUP_DECL_CPLXF(33)
 SUP_DECL_CPLXF(49)
 #undef SUP_DECL_CPLXF
+#define SUP_DECL_CPLXFM(LO)                                                             \
+  hipError_t launch_cplxfm_##LO(int n, const FockParams& p, int grid, hipStream_t s);   \
+  hipError_t occupancy_cplxfm_##LO(int n, int* blocks_per_cu);
+SUP_DECL_CPLXFM(1)
+SUP_DECL_CPLXFM(17)
+#undef SUP_DECL_CPLXFM
 #define SUP_DECL_LDS(LO)                                                                  \
   hipError_t launch_lds_##LO(int n, const WalkParams& p, int grid, hipStream_t s);        \
   hipError_t occupancy_lds_##LO(int n, int m, int* blocks_per_cu);
@@ -199,6 +205,17 @@ hipError_t launch_cplx_fock_prepare(const double* U, int C, const int32_t* rows,
 // out[2k], out[2k + 1] = 2 x fock_fold over matrix k's (re, im) partials at
 // parts + 2 mats[k].chunk0 (cplx_fock.hip).
 hipError_t launch_cplx_fock_fold(const double* parts, const FockMat* mats, uint64_t K, double* out, hipStream_t s);
+
+// Collision-aware one-walk minors (walk_cplxfm.hip, 2 <= n <= 32 rows): the
+// slab's tables have n rows; the partial of output j of chunk `local` of
+// matrix M goes to p.chunk_out[2 (n M.chunk0 + j M.chunks + local)].  Its
+// tables and x(0) are launch_cplx_fock_prepare's with side 0.
+hipError_t launch_cplx_fock_minors(int n, const FockParams& p, int grid, hipStream_t s);
+hipError_t cplx_fock_minors_occupancy(int n, int* blocks_per_cu);
+// out[2 (k n + j)], [.. + 1] = 2 x fock_fold over output j of matrix k's
+// partials at parts + 2 (n mats[k].chunk0 + j mats[k].chunks) (cplx_fock.hip).
+hipError_t launch_cplx_fock_minors_fold(const double* parts, const FockMat* mats, uint64_t K, int n, double* out,
+                                        hipStream_t s);
 
 // Fixed-order pairwise reduction of `count` doubles into *out (64-way passes,
 // zero padded; mirrored by oracle/oracle.c orc_pairwise_reduce).  `scratch`

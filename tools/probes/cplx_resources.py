@@ -8,7 +8,8 @@ the walk loop (the innermost loop with the most fp64 VALU instructions: one odd
 + one even Gray step, 2(6N - 2) of them; the collision-aware walk's loop is one
 step, 6N of them: 2N column adds, 4(N - 1) for the product, 4 for acc += w term;
 the one-walk minors' loop is 2(16N - 24): per step 2N column adds, 12N - 24 for
-the prefix/suffix chain, 2N accumulates)
+the prefix/suffix chain, 2N accumulates; the collision-aware minors' loop is
+one step, 16N - 20: those and 4 multiplies by the state's weight)
 with its scratch instructions, AGPR
 moves, v_mov and readlane / writelane, and the scratch instructions of the
 whole kernel.
@@ -16,6 +17,7 @@ whole kernel.
   python tools/probes/cplx_resources.py batch > profiles/complex_batch/walk_cplx_batch_resources.log
   python tools/probes/cplx_resources.py fock > profiles/complex_fock/walk_cplx_fock_resources.log
   python tools/probes/cplx_resources.py minors > profiles/complex_minors/walk_cplx_minors_resources.log
+  python tools/probes/cplx_resources.py fock_minors > profiles/complex_fock_minors/walk_cplx_fock_minors_resources.log
   python tools/probes/cplx_resources.py single --ranges 1_16 17_32   # walk_cplx<N>, to diff against its log
 """
 import argparse
@@ -29,9 +31,11 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "sup
 KERNELS = {"batch": ("walk_cplxb.hip", "walk_cplx_batch", ["1_16", "17_32"]),
            "single": ("walk_cplx.hip", "walk_cplx", ["1_16", "17_32", "33_48", "49_64"]),
            "minors": ("walk_cplxm.hip", "walk_cplx_minors", ["1_16", "17_32"]),
+           "fock_minors": ("walk_cplxfm.hip", "walk_cplx_fock_minors", ["1_16", "17_32"]),
            "fock": ("walk_cplxf.hip", "walk_cplx_fock", ["1_16", "17_32", "33_48", "49_64"])}
 # fp64 VALU instructions of the walk loop at order n, and how the logs name that count
 LOOP = {"fock": (lambda n: 6 * n, "6N", "one step"),
+        "fock_minors": (lambda n: 16 * n - 20, "16N-20", "one walked step"),
         "minors": (lambda n: 2 * (16 * n - 24), "2(16N-24)", "one odd + one even Gray step")}
 loop_f64, loop_name, loop_what = LOOP.get(sys.argv[1] if len(sys.argv) > 1 else "", (
     lambda n: 2 * (6 * n - 2), "2(6N-2)", "one odd + one even Gray step"))
@@ -107,6 +111,16 @@ if args.kernel == "fock":
           f"{'holds at every N' if not bad else 'FAILS at N = ' + ', '.join(map(str, bad))}")
     print(f"# VGPRs spilled outside the walk loop (chunk start; to scratch where scratch_bytes > 0, else to AGPRs): "
           f"{'none' if not out else 'N = ' + ', '.join(map(str, out))}")
+elif args.kernel == "fock_minors":
+    # no scratch anywhere in the kernel; VGPRs the allocator moved to AGPRs are listed, not hidden
+    bad = [n for n in sorted(rows) if not re.search(rf"\| {loop_f64(n)} 0 ", rows[n]) or rows[n].split()[7] != "0"
+           or rows[n].split()[-1] != "0"]
+    out = [n for n in sorted(rows) if rows[n].split()[5] != "0"]
+    moves = [n for n in sorted(rows) if rows[n].split("|")[1].split()[2] != "0"]
+    print(f"# condition (0 scratch bytes, no scratch instruction in the kernel, walk loop = {loop_name} fp64 "
+          f"instructions): {'holds at every N' if not bad else 'FAILS at N = ' + ', '.join(map(str, bad))}")
+    print(f"# VGPRs spilled to AGPRs (scratch_bytes = 0): {'none' if not out else 'N = ' + ', '.join(map(str, out))}")
+    print(f"# AGPR moves in the walk loop: {'none' if not moves else 'N = ' + ', '.join(map(str, moves))}")
 else:
     print(f"# condition (0 spilled VGPRs, 0 scratch bytes, loop = {loop_name} fp64 instructions, no scratch in it): "
           f"{'holds at every N' if not bad else 'FAILS at N = ' + ', '.join(map(str, bad))}")

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SUP_ABI_VERSION 17  /* 17: sup_perman_complex_fock_minors, sup_perman_complex_fock_minors_plan, sup_boson_sample_fock; 16: sup_plan_census; 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
+#define SUP_ABI_VERSION 18  /* 18: sup_perman_complex_quad, sup_perman_complex_quad_range, SUP_CPLX_QUAD_MAX_DEVICE_N; 17:sup_perman_complex_fock_minors, sup_perman_complex_fock_minors_plan, sup_boson_sample_fock; 16: sup_plan_census; 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SUP_OK            0
@@ -379,6 +379,49 @@ int sup_perman_complex(const double* mat, int n, const sup_opts* o, int on_cpu,
 int sup_perman_complex_range(const double* mat, int n, uint64_t c0, uint64_t c1,
                              const sup_opts* o, int on_cpu,
                              double* out_re, double* out_im, sup_stats* st);
+
+/* The permanent of a complex fp64 matrix in double-double (ABI 18): the
+ * higher-precision result the fp64 complex entries are judged against, as
+ * sup_perman_quad is for the real ones.  mat as sup_perman_complex's (n x n
+ * row-major interleaved fp64, n in [1, 64]); out = 4 doubles, re_hi, re_lo,
+ * im_hi, im_lo: Re perm = re_hi + re_lo, Im perm = im_hi + im_lo, each a
+ * normalised pair (~100 bits).  sup_perman_complex's plan and wave-chunks
+ * (default layout, or o->walk_log2 walk bits) with every value a complex
+ * double-double (walk_cplxdd.hip, cxdd.hpp); the start vector's row sums are
+ * accumulated in double-double.  The whole sum is scaled by 4(n&1) - 2,
+ * exactly.  o->gpu_num devices from o->device_id split the wave-chunks
+ * statically; on_cpu = 1 runs the same operations in the same order on
+ * o->threads host threads.  Chunk partials are combined in one fixed pairwise
+ * tree over the chunk index (double-double adds per part): bit-identical for
+ * any device count, split or thread count.
+ * The device walk holds 8n registers of state per lane and serves n <=
+ * SUP_CPLX_QUAD_MAX_DEVICE_N, the largest order (contiguous from 1) whose
+ * kernel compiles without scratch memory; the host twin serves every n <= 64.
+ * Checks, in this order: a null pointer, n outside [1, 64] or o->walk_log2
+ * outside [0, 31]: SUP_EINVAL; on_cpu = 0 and n above the cap:
+ * SUP_EUNSUPPORTED, the message naming the cap (on any machine, with or
+ * without a device: no silent CPU fallback); on_cpu = 0 and no device:
+ * SUP_ENODEV.  Non-finite input propagates.
+ * st: kernel_ms, wall_ms, gray_steps, devices_used, lane_bits, walk_bits,
+ * grid, est_ops_per_step = 86n - 28: 18n for the column add, 68(n-1) for the
+ * product, 40 for the accumulate, in dd.hpp's nominal op counts, as
+ * sup_perman_quad's 16n + 13 (its column add is 10 instructions where dd.hpp
+ * says 9: the kernel's loop holds 88n - 28 fp64 instructions per step). */
+#define SUP_CPLX_QUAD_MAX_DEVICE_N 40
+int sup_perman_complex_quad(const double* mat, int n, const sup_opts* o, int on_cpu,
+                            double* out /* 4: re_hi, re_lo, im_hi, im_lo */, sup_stats* st);
+/* The part of that sum from wave-chunks [c0, c1) of the plan (o->walk_log2
+ * honoured; chunks, subsets and sign convention as sup_perman_quad_range's
+ * with the identity column map), folded by the pairwise tree over c - c0 (an
+ * odd last element moves up as it is), NOT scaled by 4(n&1) - 2.  Aligned
+ * power-of-two ranges folded pairwise in order (double-double adds per part),
+ * then scaled, reproduce sup_perman_complex_quad's bits.  One device
+ * (o->device_id; o->gpu_num is not used) or host threads.  c0 == c1: zeros.
+ * c0 > c1 or c1 beyond the plan's chunks: SUP_EINVAL; the other checks and st
+ * as sup_perman_complex_quad's (gray_steps = (c1 - c0) 2^(lane_bits +
+ * walk_bits)). */
+int sup_perman_complex_quad_range(const double* mat, int n, uint64_t c0, uint64_t c1, const sup_opts* o,
+                                  int on_cpu, double* out /* 4 */, sup_stats* st);
 
 /* Many complex permanents in one call (ABI 12): boson-sampling simulators
  * evaluate 10^4..10^7 permanents of n x n submatrices (n ~ 8..28) of one

@@ -20,7 +20,7 @@ from ._lib import (KERNEL_DENSE, KERNEL_SKIPPER, KERNEL_SPARYSER, LEAF_FN, SCHED
                    SCHED_STATIC, SupApproxResult, SupError, SupOpts, SupReduceOpts, SupStats)
 
 __all__ = [
-    "perman", "perman_cpu", "perman_exact", "perman_exact_range", "perman_quad", "perman_quad_range", "perman_complex", "perman_complex_range", "perman_complex_batch", "perman_complex_submatrices", "perman_complex_fock", "perman_complex_fock_plan", "perman_complex_fock_minors", "perman_complex_fock_minors_submatrices",
+    "perman", "perman_cpu", "perman_exact", "perman_exact_range", "perman_quad", "perman_quad_range", "perman_complex", "perman_complex_range", "perman_complex_quad", "perman_complex_quad_range", "COMPLEX_QUAD_MAX_DEVICE_N", "perman_complex_batch", "perman_complex_submatrices", "perman_complex_fock", "perman_complex_fock_plan", "perman_complex_fock_minors", "perman_complex_fock_minors_submatrices",
            "perman_complex_fock_minors_plan", "perman_complex_minors", "perman_complex_minors_submatrices", "perman_complex_minors_range", "boson_sample", "read_mtx_complex", "partial", "perman_shard", "plan_info", "plan_census", "CENSUS_CLASSES", "plan_key", "prepare", "read_matrix", "read_mtx", "sort_order",
     "skip_order", "compress", "decompose", "perman_reduced", "approx", "grid_graph", "ALGOS_APPROX",
     "nw_start", "device_count", "rccl_devices", "layout", "ShardCall", "SupError", "ALGOS_DENSE", "ALGOS_SPARSE",
@@ -290,6 +290,46 @@ def perman_complex_range(mat, c0: int, c1: int, cpu: bool = False, threads: int 
     _lib.check(lib.sup_perman_complex_range(a.ctypes.data, n, int(c0), int(c1), C.byref(o), int(bool(cpu)),
                                             C.byref(re), C.byref(im), C.byref(st)), "perman_complex_range")
     v = complex(re.value, im.value)
+    return (v, st.as_dict()) if return_stats else v
+
+
+# Largest order the device walk of perman_complex_quad serves (SUP_CPLX_QUAD_MAX_DEVICE_N).
+COMPLEX_QUAD_MAX_DEVICE_N = 40
+
+
+def perman_complex_quad(mat, gpu_num: int = 1, device_id: int = 0, cpu: bool = False, threads: int = 16,
+                        walk_log2: int = 0, return_stats: bool = False):
+    """The permanent of a complex matrix in double-double (~100 bits per part):
+    ``((re_hi, re_lo), (im_hi, im_lo))``, Re = re_hi + re_lo, Im = im_hi + im_lo.
+    perman_complex's plan and wave-chunks with every value a complex
+    double-double (walk_cplxdd.hip) on gpu_num devices, or (cpu=True) its host
+    twin on `threads` threads — bit-identical either way, for any device or
+    thread count.  The device serves n <= COMPLEX_QUAD_MAX_DEVICE_N; above it
+    SupError (SUP_EUNSUPPORTED) unless cpu=True (the host twin serves n <= 64)."""
+    a, n = _cmat(mat)
+    lib = _lib.load()
+    o = _opts(gpu_num=gpu_num, device_id=device_id, threads=threads, walk_log2=walk_log2)
+    out, st = (C.c_double * 4)(), SupStats()
+    _lib.check(lib.sup_perman_complex_quad(a.ctypes.data, n, C.byref(o), int(bool(cpu)), out, C.byref(st)),
+               "perman_complex_quad")
+    v = ((out[0], out[1]), (out[2], out[3]))
+    return (v, st.as_dict()) if return_stats else v
+
+
+def perman_complex_quad_range(mat, c0: int, c1: int, cpu: bool = False, threads: int = 16, device_id: int = 0,
+                              walk_log2: int = 0, return_stats: bool = False):
+    """The part of perman_complex_quad's sum from wave-chunks [c0, c1) of its
+    plan, folded pairwise over c - c0 (double-double adds per part) and not
+    scaled by 4(n&1)-2, as ``((re_hi, re_lo), (im_hi, im_lo))``: aligned
+    power-of-two ranges folded pairwise in order, then scaled, reproduce
+    perman_complex_quad's bits.  One device, or (cpu=True) host threads."""
+    a, n = _cmat(mat)
+    lib = _lib.load()
+    o = _opts(device_id=device_id, threads=threads, walk_log2=walk_log2)
+    out, st = (C.c_double * 4)(), SupStats()
+    _lib.check(lib.sup_perman_complex_quad_range(a.ctypes.data, n, int(c0), int(c1), C.byref(o), int(bool(cpu)), out,
+                                                 C.byref(st)), "perman_complex_quad_range")
+    v = ((out[0], out[1]), (out[2], out[3]))
     return (v, st.as_dict()) if return_stats else v
 
 

@@ -37,6 +37,7 @@ EXPORTS = [
     "sup_prepare", "sup_plan_key", "sup_perman_exact", "sup_perman_exact_range", "sup_perman_reduced_exact",
     "sup_perman_quad", "sup_perman_quad_range",
     "sup_perman_reduced_quad", "sup_perman_complex", "sup_perman_complex_range", "sup_read_mtx_complex",
+    "sup_perman_complex_quad", "sup_perman_complex_quad_range",
     "sup_perman_complex_batch", "sup_perman_complex_submatrices",
     "sup_perman_complex_fock", "sup_perman_complex_fock_plan",
     "sup_perman_complex_minors", "sup_perman_complex_minors_range", "sup_boson_sample",
@@ -135,7 +136,7 @@ def load() -> C.CDLL:
             build()
         lib = C.CDLL(LIB_PATH)
         _declare(lib)
-        if lib.sup_abi_version() != 17:
+        if lib.sup_abi_version() != 18:
             raise RuntimeError("libsuperman_hip.so ABI version mismatch")
         _lib = lib
         return lib
@@ -166,6 +167,9 @@ def _declare(lib: C.CDLL) -> None:
     lib.sup_perman_complex.argtypes = [P, I, C.POINTER(SupOpts), I, C.POINTER(D), C.POINTER(D), C.POINTER(SupStats)]
     lib.sup_perman_complex_range.argtypes = [P, I, C.c_uint64, C.c_uint64, C.POINTER(SupOpts), I, C.POINTER(D),
                                              C.POINTER(D), C.POINTER(SupStats)]
+    lib.sup_perman_complex_quad.argtypes = [P, I, C.POINTER(SupOpts), I, C.POINTER(D), C.POINTER(SupStats)]
+    lib.sup_perman_complex_quad_range.argtypes = [P, I, C.c_uint64, C.c_uint64, C.POINTER(SupOpts), I, C.POINTER(D),
+                                                  C.POINTER(SupStats)]
     lib.sup_perman_complex_batch.argtypes = [P, I, C.c_uint64, C.POINTER(SupOpts), I, P, C.POINTER(SupStats)]
     lib.sup_perman_complex_submatrices.argtypes = [P, I, I, P, P, I, C.c_uint64, C.POINTER(SupOpts), I, P,
                                                    C.POINTER(SupStats)]

@@ -453,6 +453,38 @@ int sup_perman_complex_range(const double* mat, int n, uint64_t c0, uint64_t c1,
   return SUP_OK;
 }
 
+// The complex double-double entries (cplx_quad.cpp checks every argument).
+int sup_perman_complex_quad(const double* mat, int n, const sup_opts* o_in, int on_cpu, double* out, sup_stats* st) {
+  auto t0 = std::chrono::steady_clock::now();
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  double v[4] = {0.0, 0.0, 0.0, 0.0};
+  CplxInfo ci;
+  if (int rc = cplx_quad_perman(mat, n, o, on_cpu != 0, out ? v : nullptr, &ci)) return rc;
+  std::copy(v, v + 4, out);
+  const double wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  fill_cplx_stats(st, ci, n, 1ull << (n - 1), wall);
+  if (st) st->est_ops_per_step = 86.0 * n - 28.0;
+  return SUP_OK;
+}
+
+int sup_perman_complex_quad_range(const double* mat, int n, uint64_t c0, uint64_t c1, const sup_opts* o_in, int on_cpu,
+                                  double* out, sup_stats* st) {
+  auto t0 = std::chrono::steady_clock::now();
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  double v[4] = {0.0, 0.0, 0.0, 0.0};
+  CplxInfo ci;
+  if (int rc = cplx_quad_perman_range(mat, n, c0, c1, o, on_cpu != 0, out ? v : nullptr, &ci)) return rc;
+  std::copy(v, v + 4, out);
+  const double wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  fill_cplx_stats(st, ci, n, (c1 - c0) << (ci.lay.L + ci.lay.m), wall);
+  if (st) st->est_ops_per_step = 86.0 * n - 28.0;
+  return SUP_OK;
+}
+
 // Both batched complex entries: `in` names the matrices (raw or U + index lists).
 static int complex_batch(const CplxBatchIn& in, int n, uint64_t count, const sup_opts* o_in, int on_cpu, double* out,
                          sup_stats* st) {

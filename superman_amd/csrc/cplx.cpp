@@ -122,8 +122,10 @@ cx cx_pairwise(const double* parts, uint64_t count) {
 // walk bits (n in [1, 64], o.walk_log2 in [0, 31]).
 Layout cplx_layout(int n, const sup_opts& o) { return layout_with_walk(n, o.walk_log2); }
 
+}  // namespace
+
 // The plan (column planes Re, Im in P.cols) and start vector of A, n x n
-// row-major interleaved (re, im).
+// row-major interleaved (re, im); cplx_quad.cpp walks the same plan.
 int cplx_plan(const double* A, int n, const sup_opts& o, Plan& P, std::vector<double>& x0c) {
   if (!A) {
     set_error("null matrix pointer");
@@ -151,6 +153,8 @@ int cplx_plan(const double* A, int n, const sup_opts& o, Plan& P, std::vector<do
   P.chunk_ends = 0;  // the complex walk has no chunk-end check
   return SUP_OK;
 }
+
+namespace {
 
 int need_device(const sup_opts& o, const char* who, int* ndev) {
   int rc = device_count(ndev);

@@ -979,6 +979,45 @@ int run_range_cplx(int dev, const Plan& P, const std::vector<double>& x0c, uint6
   return timed_sync(c, kernel_ms);
 }
 
+// Complex double-double walk (walk_cplxdd.hip) over wave-chunks [c0, c1) of
+// the same kind of plan (run_range_cplx's), n <= SUP_CPLX_QUAD_MAX_DEVICE_N.
+// The start vector is four blocks (re.hi, re.lo, im.hi, im.lo) in the
+// two-block walks' buffer; a wave-chunk's partial is four doubles.
+int run_range_cplxdd(int dev, const Plan& P, const std::vector<double>& x0q, uint64_t c0, uint64_t c1, double* parts,
+                     double* kernel_ms, int* grid_out) {
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (grid_out) *grid_out = 0;
+  if (c1 <= c0) return SUP_OK;
+  const size_t plane = (size_t)2 * std::max(P.n - 1, 1) * P.NP;
+  if (P.kind != kWalkDense || P.n < 1 || P.n > SUP_CPLX_QUAD_MAX_DEVICE_N || c1 > P.lay.chunks() ||
+      x0q.size() != 4 * (size_t)P.NP || P.cols.size() != 2 * plane) {
+    set_error("run_range_cplxdd: bad request");
+    return SUP_EINVAL;
+  }
+  CtxGuard guard;
+  int rc = guard.open(dev, "device buffers");
+  if (rc) return rc;
+  DeviceCtx* c = guard.c;
+  int occ = 0;
+  SUP_HIP(cplxdd_occupancy(P.n, &occ));
+  const uint64_t count = c1 - c0;
+  const uint64_t grid = capped_grid(c, occ, count);
+  if ((rc = ensure(c->d_cols, c->cols_cap, P.cols.size()))) return rc;
+  if ((rc = ensure(c->d_x0dd, c->x0dd_cap, x0q.size()))) return rc;
+  if ((rc = ensure(c->d_chunk, c->chunk_cap, (size_t)(4 * count)))) return rc;
+  hipStream_t s = c->stream;
+  if ((rc = upload_walk_tables(c, P, c->d_x0dd, x0q))) return rc;
+  WalkParams p = walk_params(P, c->d_cols, c->d_x0dd, c0, count, c->d_counter, 1, false);
+  p.chunk_out = c->d_chunk;
+  SUP_HIP(hipEventRecord(c->ev0, s));
+  SUP_ON_DEVICE(c->dev, "complex double-double walk launch");
+  SUP_HIP(launch_cplxdd(P.n, p, (int)grid, s));
+  SUP_HIP(hipEventRecord(c->ev1, s));
+  SUP_HIP(hipMemcpyAsync(parts, c->d_chunk, 4 * count * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (grid_out) *grid_out = (int)grid;
+  return timed_sync(c, kernel_ms);
+}
+
 // Batched complex walk (walk_cplxb.hip, cplx_batch.hip) of matrices [k0, k1)
 // of `in` (order n <= 32, layout lay) on device `dev`, in slabs of K matrices:
 // per slab one upload of its raw matrices (or its index lists; U goes up once

@@ -527,6 +527,33 @@ int cplx_perman(const double* A, int n, const sup_opts& o, bool on_cpu, double* 
 // not scaled by 4(n&1) - 2; one device (o.device_id) or host threads.
 int cplx_perman_range(const double* A, int n, uint64_t c0, uint64_t c1, const sup_opts& o, bool on_cpu, double* re,
                       double* im, CplxInfo* info);
+// The complex plan of A (n x n row-major interleaved; cplx.cpp): the dense
+// identity plan of Re A in the default layout or with o.walk_log2 walk bits,
+// P.cols = its column table followed by Im A's, and the fp64 start vector x0c
+// (re block, im block).  A null, n outside [1, 64] or o.walk_log2 outside
+// [0, 31]: SUP_EINVAL.
+int cplx_plan(const double* A, int n, const sup_opts& o, Plan& P, std::vector<double>& x0c);
+
+// ---- complex double-double walk (cplx_quad.cpp, walk_cplxdd.hip) ----
+// Wave-chunk partials (re.hi, re.lo, im.hi, im.lo) of chunks [c0, c1) of the
+// complex plan P (cplx_plan's) with the double-double start vector x0q (4 NP:
+// re.hi, re.lo, im.hi, im.lo blocks) into parts[4 (c - c0) + {0..3}]: on
+// device `dev` (n <= SUP_CPLX_QUAD_MAX_DEVICE_N, else SUP_EINVAL; *grid =
+// blocks launched), or on host threads (every n <= 64, bit-identical).
+int run_range_cplxdd(int dev, const Plan& P, const std::vector<double>& x0q, uint64_t c0, uint64_t c1, double* parts,
+                     double* kernel_ms, int* grid = nullptr);
+void cpu_cplxdd_range(const Plan& P, const std::vector<double>& x0q, uint64_t c0, uint64_t c1, int threads,
+                      double* parts);
+// Permanent of the complex matrix A in double-double (sup_perman_complex_quad):
+// out = re.hi, re.lo, im.hi, im.lo.  Checks in this order: arguments
+// (SUP_EINVAL), then with on_cpu false n above the device cap
+// (SUP_EUNSUPPORTED), then the device (SUP_ENODEV).
+int cplx_quad_perman(const double* A, int n, const sup_opts& o, bool on_cpu, double* out, CplxInfo* info);
+// The part of its sum from wave-chunks [c0, c1), folded pairwise over c - c0
+// with dd_add per part, not scaled by 4(n&1) - 2; one device (o.device_id) or
+// host threads.
+int cplx_quad_perman_range(const double* A, int n, uint64_t c0, uint64_t c1, const sup_opts& o, bool on_cpu,
+                           double* out, CplxInfo* info);
 
 // ---- batched complex permanents (cplx.cpp; walk_cplxb.hip, cplx_batch.hip) ----
 // `count` matrices of order n (host pointers): `mats`, count x 2 n^2 doubles,

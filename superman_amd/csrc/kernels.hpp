@@ -79,7 +79,15 @@ SUP_DECL_CPLX(17)
 SUP_DECL_CPLX(33)
 SUP_DECL_CPLX(49)
 #undef SUP_DECL_CPLX
-#define SUP_DECL_CPLXB(LO)                                                                        \
+// walk_cplxdd.hip is instantiated up to SUP_CPLX_QUAD_MAX_DEVICE_N = 40 only: its third range is 33..40
+#define SUP_DECL_CPLXDD(LO)                                                              \
+  hipError_t launch_cplxdd_##LO(int n, const WalkParams& p, int grid, hipStream_t s);   \
+  hipError_t occupancy_cplxdd_##LO(int n, int* blocks_per_cu);
+SUP_DECL_CPLXDD(1)
+SUP_DECL_CPLXDD(17)
+SUP_DECL_CPLXDD(33)
+#undef SUP_DECL_CPLXDD
+#define SUP_DECL_CPLXB(LO)                                                                       \
   hipError_t launch_cplxb_##LO(int n, const WalkParams& p, int hbits, int grid, hipStream_t s); \
   hipError_t occupancy_cplxb_##LO(int n, int* blocks_per_cu);
 SUP_DECL_CPLXB(1)
@@ -151,6 +159,13 @@ hipError_t dd_blocked_occupancy(int n, int* blocks_per_cu);
 // p.chunk_out = 2 doubles (re, im) per wave-chunk.
 hipError_t launch_cplx(int n, const WalkParams& p, int grid, hipStream_t s);
 hipError_t cplx_occupancy(int n, int* blocks_per_cu);
+
+// Complex double-double dense walk (walk_cplxdd.hip), n <=
+// SUP_CPLX_QUAD_MAX_DEVICE_N (larger: hipErrorInvalidValue): p.cols as
+// launch_cplx's; p.x0 = 4 NP doubles (re.hi, re.lo, im.hi, im.lo blocks);
+// p.chunk_out = 4 doubles (re.hi, re.lo, im.hi, im.lo) per wave-chunk.
+hipError_t launch_cplxdd(int n, const WalkParams& p, int grid, hipStream_t s);
+hipError_t cplxdd_occupancy(int n, int* blocks_per_cu);
 
 // Batched complex walk (walk_cplxb.hip, n <= 32): the wave-chunks of
 // p.chunk_count >> hbits matrices in one queue; global chunk a is chunk

@@ -24,6 +24,12 @@
 // complex fp64 values on -d devices from -l with -g, on -t host threads with
 // -c; prints "Permanent: <re> <im>".  It does not combine with -s, -o, -u,
 // -E, -q, -a, -b, -i or -r.
+// --complex-quad (no short letter): the same file through
+// sup_perman_complex_quad, the complex walk in double-double (on the device up
+// to n = SUP_CPLX_QUAD_MAX_DEVICE_N, on -t host threads with -c up to 64);
+// prints "Permanent (double-double): <re_hi> <re_lo> <im_hi> <im_lo>".  Refused
+// with the options --complex is refused with; --complex beside it changes
+// nothing.
 #include <getopt.h>
 
 #include <chrono>
@@ -42,7 +48,7 @@ namespace {
 struct Cli {
   bool generic = true, dense = true, approximation = false, gpu = false, cpu = false, grid_graph = false;
   bool rccl = false, verbose = false, compression = false, exact = false, quad = false;
-  bool half_calc = false, half_store = false, complex = false, preprocessing_given = false, gpu_num_given = false;
+  bool half_calc = false, half_store = false, complex = false, complex_quad = false, preprocessing_given = false, gpu_num_given = false;
   int gpu_num = 2, threads = 16, perman_algo = 1, preprocessing = 0, device = 0, reps = 1;
   double scaling = -1.0;
   long number_of_times = 100000;  // main.cu:338-344 defaults
@@ -130,8 +136,10 @@ int run_approx(const Cli& c) {
 }
 
 // --complex: the complex fp64 walk (sup_perman_complex) of a MatrixMarket
-// `complex` file; same line shape as -q.
+// `complex` file; same line shape as -q.  --complex-quad: the same file
+// through sup_perman_complex_quad (the walk in double-double).
 int run_complex(const Cli& c) {
+  const char* flag = c.complex_quad ? "--complex-quad" : "--complex";
   const struct {
     bool on;
     const char* opt;
@@ -140,7 +148,7 @@ int run_complex(const Cli& c) {
                  {!c.generic, "-b"},     {c.grid_graph, "-i"},   {c.preprocessing_given, "-r"}};
   for (const auto& r : refused)
     if (r.on) {
-      std::fprintf(stderr, "perman: --complex does not combine with %s\n", r.opt);
+      std::fprintf(stderr, "perman: %s does not combine with %s\n", flag, r.opt);
       return 1;
     }
   double* mat = nullptr;
@@ -152,17 +160,25 @@ int run_complex(const Cli& c) {
   o.device_id = c.device;
   o.threads = c.threads;
   double re = 0.0, im = 0.0;
+  double q[4] = {0.0, 0.0, 0.0, 0.0};  // --complex-quad: re_hi, re_lo, im_hi, im_lo
   sup_stats st;
   int rc = SUP_OK;
   const auto t0 = std::chrono::steady_clock::now();
   for (int rep = 0; rep < c.reps && rc == SUP_OK; ++rep)
-    rc = sup_perman_complex(mat, n, &o, c.gpu ? 0 : 1, &re, &im, &st);
+    rc = c.complex_quad ? sup_perman_complex_quad(mat, n, &o, c.gpu ? 0 : 1, q, &st)
+                        : sup_perman_complex(mat, n, &o, c.gpu ? 0 : 1, &re, &im, &st);
   const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / (double)c.reps;
   sup_free(mat);
-  if (rc != SUP_OK) return fail("complex permanent");
-  std::cout << "Result: " << (c.gpu ? "gpu_perman64_complex" : "cpu_perman64_complex") << " " << re << " " << im
-            << " in " << sec << std::endl;
-  std::printf("Permanent: %.17e %.17e\n", re, im);
+  if (rc != SUP_OK) return fail(c.complex_quad ? "complex double-double permanent" : "complex permanent");
+  if (c.complex_quad) {
+    std::cout << "Result: " << (c.gpu ? "gpu_perman64_complex_quad" : "cpu_perman64_complex_quad") << " " << q[0]
+              << " " << q[2] << " in " << sec << std::endl;
+    std::printf("Permanent (double-double): %.17e %.17e %.17e %.17e\n", q[0], q[1], q[2], q[3]);
+  } else {
+    std::cout << "Result: " << (c.gpu ? "gpu_perman64_complex" : "cpu_perman64_complex") << " " << re << " " << im
+              << " in " << sec << std::endl;
+    std::printf("Permanent: %.17e %.17e\n", re, im);
+  }
   if (c.verbose)
     std::printf("Stats: devices %d kernel_ms %.3f wall_ms %.3f lanes %d walk %d grid %d\n", st.devices_used,
                 st.kernel_ms, st.wall_ms, st.lane_bits, st.walk_bits, st.grid);
@@ -190,6 +206,7 @@ int main(int argc, char** argv) {
                                         {"halfCalc", 0, NULL, 'h'},      {"halfStore", 0, NULL, 'w'},
                                         {"gridMultip", 1, NULL, 'e'},    {"checkpoint", 1, NULL, 'C'},
                                         {"complex", 0, NULL, 1000},
+                                        {"complex-quad", 0, NULL, 1001},
                                         {NULL, 0, NULL, 0}};
   int opt;
   auto need_arg = [&](char o) -> bool {
@@ -226,6 +243,7 @@ int main(int argc, char** argv) {
       case 'E': c.exact = true; break;
       case 'q': c.quad = true; break;
       case 1000: c.complex = true; break;
+      case 1001: c.complex_quad = true; break;
       case 'v': c.verbose = true; break;
       // v2 flags (revised_perman/main.cpp:1431-1460): -w stores the matrix in
       // single precision (the permanent of the float-rounded entries); -h asks
@@ -253,7 +271,7 @@ int main(int argc, char** argv) {
   }
   for (int i = optind; i < argc; ++i) std::printf("Non-option argument %s\n", argv[i]);
   if (!c.cpu && !c.gpu) c.gpu = true;  // main.cu:482-484
-  if (c.complex) return run_complex(c);
+  if (c.complex || c.complex_quad) return run_complex(c);
   if (c.grid_graph || c.approximation) return run_approx(c);
 
   void* mat = nullptr;

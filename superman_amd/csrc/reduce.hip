@@ -6,6 +6,7 @@
 // partials stay in HBM and are folded on the device by 64-way pairwise passes
 // (one wave per 64 values, ascending-xor butterfly), so only 8 bytes leave the
 // device and the result does not depend on grid size or device count.
+#include "../../include/superman.h"
 #include "kernels.hpp"
 #include "walk_common.hpp"
 
@@ -293,6 +294,24 @@ hipError_t launch_cplx(int n, const WalkParams& p, int grid, hipStream_t s) {
 hipError_t cplx_occupancy(int n, int* blocks_per_cu) {
   if (n < 1 || n > 64) return hipErrorInvalidValue;
   SUP_DISPATCH(cplx, occupancy, n, blocks_per_cu)
+}
+
+// walk_cplxdd.hip: three ranges, the last 33..SUP_CPLX_QUAD_MAX_DEVICE_N
+static_assert(SUP_CPLX_QUAD_MAX_DEVICE_N > 32 && SUP_CPLX_QUAD_MAX_DEVICE_N <= 48,
+              "walk_cplxdd's third range is 33..SUP_CPLX_QUAD_MAX_DEVICE_N (Makefile)");
+#define SUP_DISPATCH_CPLXDD(FN, ...)                  \
+  if (n <= 16) return FN##_cplxdd_1(__VA_ARGS__);     \
+  if (n <= 32) return FN##_cplxdd_17(__VA_ARGS__);    \
+  return FN##_cplxdd_33(__VA_ARGS__);
+
+hipError_t launch_cplxdd(int n, const WalkParams& p, int grid, hipStream_t s) {
+  if (n < 1 || n > SUP_CPLX_QUAD_MAX_DEVICE_N) return hipErrorInvalidValue;
+  SUP_DISPATCH_CPLXDD(launch, n, p, grid, s)
+}
+
+hipError_t cplxdd_occupancy(int n, int* blocks_per_cu) {
+  if (n < 1 || n > SUP_CPLX_QUAD_MAX_DEVICE_N) return hipErrorInvalidValue;
+  SUP_DISPATCH_CPLXDD(occupancy, n, blocks_per_cu)
 }
 
 hipError_t exact_occupancy(int n, int g, int* blocks_per_cu) {

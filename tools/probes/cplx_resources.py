@@ -9,7 +9,11 @@ the walk loop (the innermost loop with the most fp64 VALU instructions: one odd
 step, 6N of them: 2N column adds, 4(N - 1) for the product, 4 for acc += w term;
 the one-walk minors' loop is 2(16N - 24): per step 2N column adds, 12N - 24 for
 the prefix/suffix chain, 2N accumulates; the collision-aware minors' loop is
-one step, 16N - 20: those and 4 multiplies by the state's weight)
+one step, 16N - 20: those and 4 multiplies by the state's weight; the complex
+double-double walk's loop is 2(88N - 28): per step 20N for the column adds
+(dd_add_d is 10 instructions: a 6-instruction two_sum, an add, a fast_two_sum;
+dd.hpp's nominal count, which est_ops_per_step = 86N - 28 follows, says 9),
+68(N - 1) for the product, 40 for the accumulate)
 with its scratch instructions, AGPR
 moves, v_mov and readlane / writelane, and the scratch instructions of the
 whole kernel.
@@ -18,6 +22,7 @@ whole kernel.
   python tools/probes/cplx_resources.py fock > profiles/complex_fock/walk_cplx_fock_resources.log
   python tools/probes/cplx_resources.py minors > profiles/complex_minors/walk_cplx_minors_resources.log
   python tools/probes/cplx_resources.py fock_minors > profiles/complex_fock_minors/walk_cplx_fock_minors_resources.log
+  python tools/probes/cplx_resources.py quad > profiles/complex_quad/walk_cplxdd_resources.log
   python tools/probes/cplx_resources.py single --ranges 1_16 17_32   # walk_cplx<N>, to diff against its log
 """
 import argparse
@@ -32,11 +37,13 @@ KERNELS = {"batch": ("walk_cplxb.hip", "walk_cplx_batch", ["1_16", "17_32"]),
            "single": ("walk_cplx.hip", "walk_cplx", ["1_16", "17_32", "33_48", "49_64"]),
            "minors": ("walk_cplxm.hip", "walk_cplx_minors", ["1_16", "17_32"]),
            "fock_minors": ("walk_cplxfm.hip", "walk_cplx_fock_minors", ["1_16", "17_32"]),
+           "quad": ("walk_cplxdd.hip", "walk_cplxdd", ["1_16", "17_32", "33_40"]),
            "fock": ("walk_cplxf.hip", "walk_cplx_fock", ["1_16", "17_32", "33_48", "49_64"])}
 # fp64 VALU instructions of the walk loop at order n, and how the logs name that count
 LOOP = {"fock": (lambda n: 6 * n, "6N", "one step"),
         "fock_minors": (lambda n: 16 * n - 20, "16N-20", "one walked step"),
-        "minors": (lambda n: 2 * (16 * n - 24), "2(16N-24)", "one odd + one even Gray step")}
+        "minors": (lambda n: 2 * (16 * n - 24), "2(16N-24)", "one odd + one even Gray step"),
+        "quad": (lambda n: 2 * (88 * n - 28), "2(88N-28)", "one odd + one even Gray step")}
 loop_f64, loop_name, loop_what = LOOP.get(sys.argv[1] if len(sys.argv) > 1 else "", (
     lambda n: 2 * (6 * n - 2), "2(6N-2)", "one odd + one even Gray step"))
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
@@ -44,6 +51,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 ap = argparse.ArgumentParser()
 ap.add_argument("kernel", choices=sorted(KERNELS))
 ap.add_argument("--ranges", nargs="*", default=None)
+ap.add_argument("--define", nargs="*", default=[], help="extra -D macros (NAME=VALUE), e.g. a waves-per-SIMD request")
 ap.add_argument("--hipcc", default=os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))
 args = ap.parse_args()
 src, kname, ranges = KERNELS[args.kernel]
@@ -73,7 +81,7 @@ for r in ranges:
     lo, hi = r.split("_")
     with tempfile.TemporaryDirectory() as tmp:
         asm = os.path.join(tmp, "k.s")
-        p = subprocess.run([args.hipcc, *FLAGS, f"-DSUP_N_LO={lo}", f"-DSUP_N_HI={hi}", "--cuda-device-only", "-S",
+        p = subprocess.run([args.hipcc, *FLAGS, *[f"-D{d}" for d in args.define], f"-DSUP_N_LO={lo}", f"-DSUP_N_HI={hi}", "--cuda-device-only", "-S",
                             "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, src), "-o", asm],
                            capture_output=True, text=True, cwd=CSRC)
         if p.returncode:

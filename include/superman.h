@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SUP_ABI_VERSION 18  /* 18: sup_perman_complex_quad, sup_perman_complex_quad_range, SUP_CPLX_QUAD_MAX_DEVICE_N; 17:sup_perman_complex_fock_minors, sup_perman_complex_fock_minors_plan, sup_boson_sample_fock; 16: sup_plan_census; 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
+#define SUP_ABI_VERSION 19  /* 19: sup_perman_complex_exact, sup_perman_complex_exact_range, SUP_CPLX_EXACT_MAX_DEVICE_N; 18: sup_perman_complex_quad, sup_perman_complex_quad_range, SUP_CPLX_QUAD_MAX_DEVICE_N; 17:sup_perman_complex_fock_minors, sup_perman_complex_fock_minors_plan, sup_boson_sample_fock; 16: sup_plan_census; 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SUP_OK            0
@@ -422,6 +422,71 @@ int sup_perman_complex_quad(const double* mat, int n, const sup_opts* o, int on_
  * walk_bits)). */
 int sup_perman_complex_quad_range(const double* mat, int n, uint64_t c0, uint64_t c1, const sup_opts* o,
                                   int on_cpu, double* out /* 4 */, sup_stats* st);
+
+/* Exact permanent of a matrix of Gaussian integers (ABI 19): the complex
+ * counterpart of sup_perman_exact, the integer truth the floating complex
+ * entries are judged against.  mat as sup_perman_complex's (n x n row-major
+ * interleaved fp64, n in [1, 64]), every part an integer with |part| < 2^31
+ * and every row bound R_j = sum_c (|Re a_jc| + |Im a_jc|) < 2^31.
+ * The Ryser / Gray sum runs on 2A: X_j(S) = 2 a_j,n-1 - sum_c a_jc + 2
+ * sum_{e in S} a_je is a Gaussian integer with parts <= R_j, exact in two fp64
+ * values; T = sum_S (-1)^|S| prod_j X_j(S), |Re T|, |Im T| <= 2^(n-1) prod_j
+ * R_j, and perm = (4(n&1) - 2) T / 2^n.  Each product is formed in (Z/p)[i]
+ * for primes p < 2^pbits in exact fp64 residue arithmetic (walk_cplxexact.hip,
+ * cxexact.hpp): rows multiplied exactly in groups of G = 1 or 2 first, then a
+ * residue (u, v), |u|, |v| < 1.5 p, times a group product (c, d) with parts <=
+ * Y is (red(uc - vd), red(ud + vc)), exact while 1.5 p Y < 2^52.  G = 1: Y <
+ * 2^xbits (R_j < 2^xbits), pbits = min(42, 51 - xbits), at least 20 within the
+ * input limits; G = 2: Y <= 2 4^xbits, pbits = min(42, 51 - (2 xbits + 1)),
+ * eligible while that is at least 20; a cost model picks the cheaper.  The
+ * primes are the largest below 2^pbits, taken until their product exceeds 8
+ * times the bound on |T|; the residues of Re T and Im T are joined separately
+ * by CRT.  Both parts must be divisible by 2^(n-1): a built-in self-check (a
+ * failure is SUP_EHIP with a message, never a wrong number).
+ * sup_perman_complex's plan (default layout, identity column map; no
+ * chunk-end skipping, column-order search or prefix-blocked form).
+ * o->gpu_num devices from o->device_id split the wave-chunks statically, at
+ * most 4 primes per launch; on_cpu = 1 runs the same residue operations on
+ * o->threads host threads.  Residue sums are exact, so device and host agree
+ * residue for residue for any split.  o->cpu_worker is not used.  A zero row
+ * gives "0", "0" without a walk.
+ * out_re / out_im: signed decimal integers, NUL-terminated; out_len applies to
+ * each buffer, 640 bytes always suffice (|perm| <= prod R_j < 2^1984); a
+ * shorter buffer that does not fit is SUP_EINVAL with the needed length in the
+ * message.
+ * The device walk serves n <= SUP_CPLX_EXACT_MAX_DEVICE_N, the largest order
+ * (contiguous from 1) whose kernel compiles without scratch memory or spilled
+ * registers for both G; the host twin serves every n <= 64.
+ * Checks, in this order: a null pointer, n outside [1, 64], o->walk_log2
+ * outside [0, 31], a non-integral or non-finite part, a part or row bound out
+ * of range: SUP_EINVAL, the message naming the first offending (row, column,
+ * part) or row; on_cpu = 0 and n above the cap: SUP_EUNSUPPORTED, the message
+ * naming the cap (on any machine: no CPU fallback); on_cpu = 0 and no device:
+ * SUP_ENODEV.
+ * st: kernel_ms, wall_ms, gray_steps, devices_used, lane_bits, walk_bits,
+ * grid, seg_pair_bits = G, leaves 1, est_ops_per_step = 2n + [G = 2] 4
+ * floor(n/2) + P (10 ceil(n/G) - 2) fp64 instructions per Gray step and lane
+ * in a launch with P primes (P = min(4, primes); the column add, the exact
+ * pair products, and per prime 6 for the first reduction, 10 per further group
+ * and 2 for the accumulate); the kernel's loop holds that count with P = 4. */
+#define SUP_CPLX_EXACT_MAX_DEVICE_N 61
+int sup_perman_complex_exact(const double* mat, int n, const sup_opts* o, int on_cpu, char* out_re, char* out_im,
+                             size_t out_len, sup_stats* st);
+/* Per prime, the residues in [0, p) of Re and Im of the part of T from
+ * wave-chunks [c0, c1) of that walk (o->walk_log2 honoured; chunks, subsets
+ * and sign convention as sup_perman_complex_quad_range's), NOT scaled:
+ * disjoint ranges add modulo p, the whole range is T.  A zero row is walked
+ * like any other.  group: 0 the cost model's G, 1 or 2 forces it (SUP_EINVAL
+ * for other values, or when its primes would fall below 20 bits).  primes,
+ * res_re, res_im: `cap` entries each; more primes than cap: SUP_EINVAL before
+ * any walk; *nprimes = the count.  One device (o->device_id; o->gpu_num is
+ * not used) or host threads.  c0 == c1: zeros.  c0 > c1 or c1 beyond the
+ * plan's chunks: SUP_EINVAL; the other checks and st as
+ * sup_perman_complex_exact's (gray_steps = (c1 - c0) 2^(lane_bits +
+ * walk_bits)). */
+int sup_perman_complex_exact_range(const double* mat, int n, uint64_t c0, uint64_t c1, const sup_opts* o,
+                                   int on_cpu, int group, uint64_t* primes, uint64_t* res_re, uint64_t* res_im,
+                                   int cap, int* nprimes, sup_stats* st);
 
 /* Many complex permanents in one call (ABI 12): boson-sampling simulators
  * evaluate 10^4..10^7 permanents of n x n submatrices (n ~ 8..28) of one

@@ -20,7 +20,7 @@ from ._lib import (KERNEL_DENSE, KERNEL_SKIPPER, KERNEL_SPARYSER, LEAF_FN, SCHED
                    SCHED_STATIC, SupApproxResult, SupError, SupOpts, SupReduceOpts, SupStats)
 
 __all__ = [
-    "perman", "perman_cpu", "perman_exact", "perman_exact_range", "perman_quad", "perman_quad_range", "perman_complex", "perman_complex_range", "perman_complex_quad", "perman_complex_quad_range", "COMPLEX_QUAD_MAX_DEVICE_N", "perman_complex_batch", "perman_complex_submatrices", "perman_complex_fock", "perman_complex_fock_plan", "perman_complex_fock_minors", "perman_complex_fock_minors_submatrices",
+    "perman", "perman_cpu", "perman_exact", "perman_exact_range", "perman_quad", "perman_quad_range", "perman_complex", "perman_complex_range", "perman_complex_quad", "perman_complex_quad_range", "COMPLEX_QUAD_MAX_DEVICE_N", "perman_complex_exact", "perman_complex_exact_range", "COMPLEX_EXACT_MAX_DEVICE_N", "perman_complex_batch", "perman_complex_submatrices", "perman_complex_fock", "perman_complex_fock_plan", "perman_complex_fock_minors", "perman_complex_fock_minors_submatrices",
            "perman_complex_fock_minors_plan", "perman_complex_minors", "perman_complex_minors_submatrices", "perman_complex_minors_range", "boson_sample", "read_mtx_complex", "partial", "perman_shard", "plan_info", "plan_census", "CENSUS_CLASSES", "plan_key", "prepare", "read_matrix", "read_mtx", "sort_order",
     "skip_order", "compress", "decompose", "perman_reduced", "approx", "grid_graph", "ALGOS_APPROX",
     "nw_start", "device_count", "rccl_devices", "layout", "ShardCall", "SupError", "ALGOS_DENSE", "ALGOS_SPARSE",
@@ -330,6 +330,70 @@ def perman_complex_quad_range(mat, c0: int, c1: int, cpu: bool = False, threads:
     _lib.check(lib.sup_perman_complex_quad_range(a.ctypes.data, n, int(c0), int(c1), C.byref(o), int(bool(cpu)), out,
                                                  C.byref(st)), "perman_complex_quad_range")
     v = ((out[0], out[1]), (out[2], out[3]))
+    return (v, st.as_dict()) if return_stats else v
+
+
+# Largest order the device walk of perman_complex_exact serves (SUP_CPLX_EXACT_MAX_DEVICE_N).
+COMPLEX_EXACT_MAX_DEVICE_N = 61
+
+
+def _cmat_exact(mat, what: str) -> tuple[np.ndarray, int]:
+    """`mat` as a C-order complex128 matrix for the exact complex entries.  An
+    integer that complex128 cannot hold exactly (|v| >= 2^53: an int64, or a
+    Python int in an object array) is refused here, not rounded; what float
+    and complex arrays hold goes to the library, which checks integrality and
+    range itself."""
+    raw = np.asarray(mat)
+    if raw.dtype.kind in "iuO":
+        for idx, v in np.ndenumerate(raw):
+            if isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) and abs(int(v)) >= 1 << 53:
+                raise SupError(-1, what, f"entry {idx} = {int(v)} is not exactly representable in fp64 "
+                                         "(parts must be integers with |part| < 2^31)")
+    return _cmat(raw)
+
+
+def perman_complex_exact(mat, gpu_num: int = 1, device_id: int = 0, cpu: bool = False, threads: int = 16,
+                         return_stats: bool = False):
+    """The exact permanent of a matrix of Gaussian integers as ``(re, im)``, two
+    Python ints (sup_perman_complex_exact).  ``mat``: anything np.asarray turns
+    into an n x n complex or integer array whose parts are integers with |part|
+    < 2^31 and row sums of |Re| + |Im| below 2^31.  The Ryser / Gray sum of 2A
+    in residue arithmetic over (Z/p)[i] (walk_cplxexact.hip) on gpu_num
+    devices, or (cpu=True) its host twin on `threads` threads, joined by CRT:
+    the same integers either way.  The device serves n <=
+    COMPLEX_EXACT_MAX_DEVICE_N; above it SupError (SUP_EUNSUPPORTED) unless
+    cpu=True (the host twin serves n <= 64)."""
+    a, n = _cmat_exact(mat, "perman_complex_exact")
+    lib = _lib.load()
+    o = _opts(gpu_num=gpu_num, device_id=device_id, threads=threads)
+    re, im, st = C.create_string_buffer(640), C.create_string_buffer(640), SupStats()
+    _lib.check(lib.sup_perman_complex_exact(a.ctypes.data, n, C.byref(o), int(bool(cpu)), re, im, 640, C.byref(st)),
+               "perman_complex_exact")
+    v = (int(re.value.decode()), int(im.value.decode()))
+    return (v, st.as_dict()) if return_stats else v
+
+
+def perman_complex_exact_range(mat, c0: int, c1: int, group: int = 0, cpu: bool = False, threads: int = 16,
+                               device_id: int = 0, walk_log2: int = 0, return_stats: bool = False, cap: int = 128):
+    """Wave-chunks [c0, c1) of perman_complex_exact's walk of 2A
+    (sup_perman_complex_exact_range): ``{"primes": [...], "re": [...], "im":
+    [...]}``, per prime the residues in [0, p) of Re and Im of the range's part
+    of T (not scaled; disjoint ranges add modulo p, the whole range is T).
+    ``group``: 0 the cost model's G, or 1, 2; ``walk_log2``: walk bits (0 =
+    default layout).  One device, or (cpu=True) host threads: the same
+    residues."""
+    a, n = _cmat_exact(mat, "perman_complex_exact_range")
+    lib = _lib.load()
+    o = _opts(device_id=device_id, threads=threads, walk_log2=walk_log2)
+    size = max(int(cap), 1)
+    primes, rre, rim = np.zeros(size, np.uint64), np.zeros(size, np.uint64), np.zeros(size, np.uint64)
+    np_out, st = C.c_int(0), SupStats()
+    _lib.check(lib.sup_perman_complex_exact_range(a.ctypes.data, n, int(c0), int(c1), C.byref(o), int(bool(cpu)),
+                                                  int(group), primes.ctypes.data, rre.ctypes.data, rim.ctypes.data,
+                                                  int(cap), C.byref(np_out), C.byref(st)),
+               "perman_complex_exact_range")
+    k = np_out.value
+    v = {"primes": [int(x) for x in primes[:k]], "re": [int(x) for x in rre[:k]], "im": [int(x) for x in rim[:k]]}
     return (v, st.as_dict()) if return_stats else v
 
 

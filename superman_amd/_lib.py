@@ -38,6 +38,7 @@ EXPORTS = [
     "sup_perman_quad", "sup_perman_quad_range",
     "sup_perman_reduced_quad", "sup_perman_complex", "sup_perman_complex_range", "sup_read_mtx_complex",
     "sup_perman_complex_quad", "sup_perman_complex_quad_range",
+    "sup_perman_complex_exact", "sup_perman_complex_exact_range",
     "sup_perman_complex_batch", "sup_perman_complex_submatrices",
     "sup_perman_complex_fock", "sup_perman_complex_fock_plan",
     "sup_perman_complex_minors", "sup_perman_complex_minors_range", "sup_boson_sample",
@@ -136,7 +137,7 @@ def load() -> C.CDLL:
             build()
         lib = C.CDLL(LIB_PATH)
         _declare(lib)
-        if lib.sup_abi_version() != 18:
+        if lib.sup_abi_version() != 19:
             raise RuntimeError("libsuperman_hip.so ABI version mismatch")
         _lib = lib
         return lib
@@ -170,6 +171,10 @@ def _declare(lib: C.CDLL) -> None:
     lib.sup_perman_complex_quad.argtypes = [P, I, C.POINTER(SupOpts), I, C.POINTER(D), C.POINTER(SupStats)]
     lib.sup_perman_complex_quad_range.argtypes = [P, I, C.c_uint64, C.c_uint64, C.POINTER(SupOpts), I, C.POINTER(D),
                                                   C.POINTER(SupStats)]
+    lib.sup_perman_complex_exact.argtypes = [P, I, C.POINTER(SupOpts), I, C.c_char_p, C.c_char_p, C.c_size_t,
+                                             C.POINTER(SupStats)]
+    lib.sup_perman_complex_exact_range.argtypes = [P, I, C.c_uint64, C.c_uint64, C.POINTER(SupOpts), I, I, P, P, P, I,
+                                                   C.POINTER(I), C.POINTER(SupStats)]
     lib.sup_perman_complex_batch.argtypes = [P, I, C.c_uint64, C.POINTER(SupOpts), I, P, C.POINTER(SupStats)]
     lib.sup_perman_complex_submatrices.argtypes = [P, I, I, P, P, I, C.c_uint64, C.POINTER(SupOpts), I, P,
                                                    C.POINTER(SupStats)]

@@ -485,6 +485,63 @@ int sup_perman_complex_quad_range(const double* mat, int n, uint64_t c0, uint64_
   return SUP_OK;
 }
 
+// The exact complex entries (cplx_exact.cpp checks the matrix and the options).
+static void fill_cplx_exact_stats(sup_stats* st, const CplxExactInfo& xi, int n, uint64_t steps, double wall_ms) {
+  fill_cplx_stats(st, xi.ci, n, steps, wall_ms);
+  if (!st) return;
+  st->seg_pair_bits = (int16_t)xi.group;
+  st->est_ops_per_step = xi.est_ops;
+}
+
+int sup_perman_complex_exact(const double* mat, int n, const sup_opts* o_in, int on_cpu, char* out_re, char* out_im,
+                             size_t out_len, sup_stats* st) {
+  auto t0 = std::chrono::steady_clock::now();
+  if (!mat || !out_re || !out_im) {
+    set_error("sup_perman_complex_exact: null matrix or output pointer");
+    return SUP_EINVAL;
+  }
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  std::string re, im;
+  CplxExactInfo xi;
+  if (int rc = cplx_exact_perman(mat, n, o, on_cpu != 0, re, im, &xi)) return rc;
+  const size_t need = std::max(re.size(), im.size()) + 1;
+  if (out_len < need) {
+    set_error("sup_perman_complex_exact: out_len = " + std::to_string(out_len) + " but the result needs " +
+              std::to_string(need) + " bytes per buffer (640 always suffice)");
+    return SUP_EINVAL;
+  }
+  std::memcpy(out_re, re.c_str(), re.size() + 1);
+  std::memcpy(out_im, im.c_str(), im.size() + 1);
+  const double wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  fill_cplx_exact_stats(st, xi, n, xi.group ? 1ull << (n - 1) : 0, wall);  // group 0: a zero row, no walk
+  return SUP_OK;
+}
+
+int sup_perman_complex_exact_range(const double* mat, int n, uint64_t c0, uint64_t c1, const sup_opts* o_in,
+                                   int on_cpu, int group, uint64_t* primes, uint64_t* res_re, uint64_t* res_im,
+                                   int cap, int* nprimes, sup_stats* st) {
+  auto t0 = std::chrono::steady_clock::now();
+  if (!mat || !primes || !res_re || !res_im || !nprimes) {
+    set_error("sup_perman_complex_exact_range: null matrix or output pointer");
+    return SUP_EINVAL;
+  }
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  std::vector<uint64_t> pr, rr, ri;
+  CplxExactInfo xi;
+  if (int rc = cplx_exact_perman_range(mat, n, c0, c1, o, on_cpu != 0, group, cap, pr, rr, ri, &xi)) return rc;
+  std::copy(pr.begin(), pr.end(), primes);
+  std::copy(rr.begin(), rr.end(), res_re);
+  std::copy(ri.begin(), ri.end(), res_im);
+  *nprimes = (int)pr.size();
+  const double wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  fill_cplx_exact_stats(st, xi, n, (c1 - c0) << (xi.ci.lay.L + xi.ci.lay.m), wall);
+  return SUP_OK;
+}
+
 // Both batched complex entries: `in` names the matrices (raw or U + index lists).
 static int complex_batch(const CplxBatchIn& in, int n, uint64_t count, const sup_opts* o_in, int on_cpu, double* out,
                          sup_stats* st) {

@@ -1018,6 +1018,68 @@ int run_range_cplxdd(int dev, const Plan& P, const std::vector<double>& x0q, uin
   return timed_sync(c, kernel_ms);
 }
 
+// Exact complex residue walk (walk_cplxexact.hip) over wave-chunks [c0, c1) of
+// a complex plan of the doubled matrix (run_range_cplx's tables and start
+// vector): per prime and part, the sum of the terms mod p in [0, p).  Residue
+// sums are exact, so neither the wave a chunk lands on nor the order of the
+// per-wave sums changes the result.  The kernel takes its primes in pairs: an
+// odd count is padded with a repeat of the last prime, whose result is dropped.
+int run_range_cplxexact(int dev, const Plan& P, const std::vector<double>& x0c, int group, uint64_t c0, uint64_t c1,
+                        const std::vector<double>& primes, std::vector<uint64_t>& res_re,
+                        std::vector<uint64_t>& res_im, double* kernel_ms, int* grid_out) {
+  const int np = (int)primes.size();
+  res_re.assign(np, 0);
+  res_im.assign(np, 0);
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (grid_out) *grid_out = 0;
+  if (c1 <= c0) return SUP_OK;
+  const size_t plane = (size_t)2 * std::max(P.n - 1, 1) * P.NP;
+  if (np < 1 || np > kMaxCxPrimes || (group != 1 && group != 2) || P.kind != kWalkDense || P.n < 1 ||
+      P.n > SUP_CPLX_EXACT_MAX_DEVICE_N || c1 > P.lay.chunks() || x0c.size() != 2 * (size_t)P.NP ||
+      P.cols.size() != 2 * plane) {
+    set_error("run_range_cplxexact: bad request");
+    return SUP_EINVAL;
+  }
+  CtxGuard guard;
+  int rc = guard.open(dev, "device buffers");
+  if (rc) return rc;
+  DeviceCtx* c = guard.c;
+  int occ = 0;
+  SUP_HIP(cplxexact_occupancy(P.n, group, &occ));
+  const uint64_t count = c1 - c0;
+  const uint64_t grid = capped_grid(c, occ, count);
+  const size_t waves = (size_t)grid * kWavesPerBlock, per_wave = (size_t)2 * kMaxCxPrimes;
+  if ((rc = ensure(c->d_cols, c->cols_cap, P.cols.size()))) return rc;
+  if ((rc = ensure(c->d_x0dd, c->x0dd_cap, x0c.size()))) return rc;
+  if ((rc = ensure(c->d_wave, c->wave_cap, waves * per_wave))) return rc;
+  hipStream_t s = c->stream;
+  if ((rc = upload_walk_tables(c, P, c->d_x0dd, x0c))) return rc;
+  WalkParams p = walk_params(P, c->d_cols, c->d_x0dd, c0, count, c->d_counter, 1, false);
+  CxExactParams e{};
+  const int npad = (np + 1) & ~1;
+  for (int q = 0; q < npad; ++q) e.prime[q] = primes[std::min(q, np - 1)], e.pinv[q] = 1.0 / e.prime[q];
+  e.nprimes = npad;
+  e.wave_out = c->d_wave;
+  SUP_HIP(hipEventRecord(c->ev0, s));
+  SUP_ON_DEVICE(c->dev, "exact complex walk launch");
+  SUP_HIP(launch_cplxexact(P.n, group, p, e, (int)grid, s));
+  SUP_HIP(hipEventRecord(c->ev1, s));
+  std::vector<double> w(waves * per_wave);
+  SUP_HIP(hipMemcpyAsync(w.data(), c->d_wave, w.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (grid_out) *grid_out = (int)grid;
+  if ((rc = timed_sync(c, kernel_ms))) return rc;
+  for (int q = 0; q < np; ++q) {
+    const uint64_t pq = (uint64_t)primes[q];
+    uint64_t are = 0, aim = 0;  // waves x p < 2^64
+    for (size_t i = 0; i < waves; ++i) {
+      are = (are + (uint64_t)w[(i * kMaxCxPrimes + q) * 2]) % pq;
+      aim = (aim + (uint64_t)w[(i * kMaxCxPrimes + q) * 2 + 1]) % pq;
+    }
+    res_re[q] = are, res_im[q] = aim;
+  }
+  return SUP_OK;
+}
+
 // Batched complex walk (walk_cplxb.hip, cplx_batch.hip) of matrices [k0, k1)
 // of `in` (order n <= 32, layout lay) on device `dev`, in slabs of K matrices:
 // per slab one upload of its raw matrices (or its index lists; U goes up once

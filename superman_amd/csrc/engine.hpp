@@ -447,6 +447,15 @@ struct RangeInfo {
 };
 int exact_perman(const double* A, int n, const sup_opts& o, bool on_cpu, std::string& out, double* kernel_ms,
                  int* devices_used, int* cpu_items = nullptr, RangeInfo* info = nullptr);
+// The two halves of an exact result that the exact complex entries share
+// (exact.cpp).  The largest primes below 2^pbits, descending, until the log2
+// of their product reaches `bits`.
+void exact_take_primes(int pbits, double bits, std::vector<double>& primes);
+// The residues res[i] in [0, primes[i]) of an integer T, |T| < (prod p) / 2,
+// joined by CRT (Garner); out = (4(n&1) - 2) T / 2^n as a signed decimal
+// string.  T not divisible by 2^(n-1): SUP_EHIP, the message starting with `who`.
+int exact_crt_perman(const std::vector<double>& primes, const std::vector<uint64_t>& res, int n, const char* who,
+                     std::string& out);
 // n in [1, 64], o.walk_log2 in [0, 31] and form in [0, 2] of a range entry
 // (`who` in the messages), else SUP_EINVAL.
 int check_range_request(int n, const sup_opts& o, int form, const char* who);
@@ -554,6 +563,40 @@ int cplx_quad_perman(const double* A, int n, const sup_opts& o, bool on_cpu, dou
 // host threads.
 int cplx_quad_perman_range(const double* A, int n, uint64_t c0, uint64_t c1, const sup_opts& o, bool on_cpu,
                            double* out, CplxInfo* info);
+
+// ---- exact complex walk (cplx_exact.cpp, walk_cplxexact.hip, cxexact.hpp) ----
+// Per prime, the sums over wave-chunks [c0, c1) of Re and Im of the terms of
+// the complex plan P of the doubled matrix (cplx_plan's, start vector x0c)
+// modulo that prime, each in [0, p): on device `dev` (n <=
+// SUP_CPLX_EXACT_MAX_DEVICE_N, rows multiplied in exact groups of `group` = 1
+// or 2, at most kMaxCxPrimes primes; *grid = blocks launched), or on host
+// threads (every n <= 64; the same residues: every operation is exact).
+int run_range_cplxexact(int dev, const Plan& P, const std::vector<double>& x0c, int group, uint64_t c0, uint64_t c1,
+                        const std::vector<double>& primes, std::vector<uint64_t>& res_re,
+                        std::vector<uint64_t>& res_im, double* kernel_ms, int* grid = nullptr);
+void cpu_cplx_exact_range(const Plan& P, const std::vector<double>& x0c, int group, uint64_t c0, uint64_t c1,
+                          const std::vector<double>& primes, int threads, std::vector<uint64_t>& res_re,
+                          std::vector<uint64_t>& res_im);
+// What an exact complex call reports beside its value (sup_stats).
+struct CplxExactInfo {
+  CplxInfo ci;
+  int group = 0;         // G that ran
+  double est_ops = 0.0;  // cxe_ops_per_step(n, G, primes in a launch)
+};
+// Exact permanent of the n x n matrix of Gaussian integers A (row-major,
+// interleaved doubles holding integers) as two signed decimal strings
+// (sup_perman_complex_exact).  Checks in this order: arguments and input
+// limits (SUP_EINVAL), then with on_cpu false n above the device cap
+// (SUP_EUNSUPPORTED), then the device (SUP_ENODEV).
+int cplx_exact_perman(const double* A, int n, const sup_opts& o, bool on_cpu, std::string& re, std::string& im,
+                      CplxExactInfo* info);
+// Per prime, the residues in [0, p) of Re and Im of the part of T from
+// wave-chunks [c0, c1) (sup_perman_complex_exact_range): one device
+// (o.device_id) or host threads.  group: 0 the cost model's, or 1, 2.  More
+// than `cap` primes: SUP_EINVAL before any walk.
+int cplx_exact_perman_range(const double* A, int n, uint64_t c0, uint64_t c1, const sup_opts& o, bool on_cpu,
+                            int group, int cap, std::vector<uint64_t>& primes, std::vector<uint64_t>& res_re,
+                            std::vector<uint64_t>& res_im, CplxExactInfo* info);
 
 // ---- batched complex permanents (cplx.cpp; walk_cplxb.hip, cplx_batch.hip) ----
 // `count` matrices of order n (host pointers): `mats`, count x 2 n^2 doubles,

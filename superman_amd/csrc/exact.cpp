@@ -226,9 +226,7 @@ int exact_setup(const double* A, int n, const Layout& lay, bool whole, int form,
     }
   }
   // primes: the largest below 2^pbits, until their product exceeds 2 |T| (+ margin)
-  double bits = 0.0;
-  for (uint64_t c = (1ull << pbits) - 1; bits < logT + 2.0 + 1.0; c -= 2)
-    if (is_prime(c)) S.primes.push_back((double)c), bits += std::log2((double)c);
+  exact_take_primes(pbits, logT + 2.0 + 1.0, S.primes);
 
   Plan& P = S.P;
   std::vector<double> A2((size_t)n * n);
@@ -262,6 +260,59 @@ int exact_setup(const double* A, int n, const Layout& lay, bool whole, int form,
 }
 
 }  // namespace
+
+// The largest primes below 2^pbits, in descending order, until the log2 of
+// their product reaches `bits`.
+void exact_take_primes(int pbits, double bits, std::vector<double>& primes) {
+  double have = 0.0;
+  for (uint64_t c = (1ull << pbits) - 1; have < bits; c -= 2)
+    if (is_prime(c)) primes.push_back((double)c), have += std::log2((double)c);
+}
+
+// The residues res[i] in [0, primes[i]) of an integer T with |T| < (prod p) / 2
+// joined by CRT, and out = (4(n&1) - 2) T / 2^n as a signed decimal string.  T
+// must be divisible by 2^(n-1) (the walk's self-check): else SUP_EHIP.
+int exact_crt_perman(const std::vector<double>& primes, const std::vector<uint64_t>& res, int n, const char* who,
+                     std::string& out) {
+  const int np = (int)primes.size();
+  // Garner: mixed-radix digits v_i, then T = sum v_i prod_{j<i} p_j in [0, M)
+  std::vector<uint64_t> p(np), v(np);
+  for (int i = 0; i < np; ++i) p[i] = (uint64_t)primes[i];
+  for (int i = 0; i < np; ++i) {
+    uint64_t x = res[i] % p[i], prod = 1 % p[i], acc = 0;  // acc = value of digits < i mod p_i
+    for (int j = 0; j < i; ++j) {
+      acc = (acc + mulmod(v[j] % p[i], prod, p[i])) % p[i];
+      prod = mulmod(prod, p[j] % p[i], p[i]);
+    }
+    const uint64_t diff = (x + p[i] - acc) % p[i];
+    v[i] = mulmod(diff, powmod(prod, p[i] - 2, p[i]), p[i]);
+  }
+  // Horner: T = (...(v_{k-1} p_{k-2} + v_{k-2}) p_{k-3} + ...) p_0 + v_0
+  Big T, M, half;
+  T.mul_add(1, v[np - 1]);
+  for (int i = np - 2; i >= 0; --i) T.mul_add(p[i], v[i]);
+  M.d.assign(1, 1u);
+  for (int i = 0; i < np; ++i) M.mul_add(p[i], 0);
+  // signed: T > M/2 stands for T - M
+  half = M;
+  half.divmod(2);
+  bool neg = false;
+  if (T.cmp(half) > 0) {
+    Big t = M;
+    t.sub(T);
+    T = t;
+    neg = true;
+  }
+  // perm = (4(n&1) - 2) T / 2^n = (n odd ? 1 : -1) T / 2^(n-1)
+  if (!T.low_bits_zero(n - 1)) {
+    set_error(std::string(who) + ": self-check failed (T not divisible by 2^(n-1))");
+    return SUP_EHIP;
+  }
+  T.shr(n - 1);
+  if (!(n & 1)) neg = !neg;
+  out = (neg && !T.zero() ? "-" : "") + T.dec();
+  return SUP_OK;
+}
 
 int check_range_request(int n, const sup_opts& o, int form, const char* who) {
   if (n < 1 || n > SUP_MAX_N) {
@@ -426,42 +477,7 @@ int exact_perman(const double* A, int n, const sup_opts& o, bool on_cpu, std::st
     cpu_done = cpu ? dtook[G] : 0;
   }
 
-  // Garner: mixed-radix digits v_i, then T = sum v_i prod_{j<i} p_j in [0, M)
-  std::vector<uint64_t> p(np), v(np);
-  for (int i = 0; i < np; ++i) p[i] = (uint64_t)primes[i];
-  for (int i = 0; i < np; ++i) {
-    uint64_t x = res[i] % p[i], prod = 1 % p[i], acc = 0;  // acc = value of digits < i mod p_i
-    for (int j = 0; j < i; ++j) {
-      acc = (acc + mulmod(v[j] % p[i], prod, p[i])) % p[i];
-      prod = mulmod(prod, p[j] % p[i], p[i]);
-    }
-    const uint64_t diff = (x + p[i] - acc) % p[i];
-    v[i] = mulmod(diff, powmod(prod, p[i] - 2, p[i]), p[i]);
-  }
-  // Horner: T = (...(v_{k-1} p_{k-2} + v_{k-2}) p_{k-3} + ...) p_0 + v_0
-  Big T, M, half;
-  T.mul_add(1, v[np - 1]);
-  for (int i = np - 2; i >= 0; --i) T.mul_add(p[i], v[i]);
-  M.d.assign(1, 1u);
-  for (int i = 0; i < np; ++i) M.mul_add(p[i], 0);
-  // signed: T > M/2 stands for T - M
-  half = M;
-  half.divmod(2);
-  bool neg = false;
-  if (T.cmp(half) > 0) {
-    Big t = M;
-    t.sub(T);
-    T = t;
-    neg = true;
-  }
-  // perm = (4(n&1) - 2) T / 2^n = (n odd ? 1 : -1) T / 2^(n-1)
-  if (!T.low_bits_zero(n - 1)) {
-    set_error("sup_perman_exact: self-check failed (T not divisible by 2^(n-1))");
-    return SUP_EHIP;
-  }
-  T.shr(n - 1);
-  if (!(n & 1)) neg = !neg;
-  out = (neg && !T.zero() ? "-" : "") + T.dec();
+  if ((rc = exact_crt_perman(primes, res, n, "sup_perman_exact", out))) return rc;
   if (kernel_ms) *kernel_ms = kms;
   if (devices_used) *devices_used = used;
   if (cpu_items) *cpu_items = cpu_done;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "cplx_fock.hpp"
+#include "cxexact.hpp"
 #include "walk_batch.hpp"
 #include "walk_params.hpp"
 
@@ -87,6 +88,16 @@ SUP_DECL_CPLXDD(1)
 SUP_DECL_CPLXDD(17)
 SUP_DECL_CPLXDD(33)
 #undef SUP_DECL_CPLXDD
+// walk_cplxexact.hip: N = 1..SUP_CPLX_EXACT_MAX_DEVICE_N, g = 1 or 2
+#define SUP_DECL_CPLXEXACT(LO)                                                                                \
+  hipError_t launch_cplxexact_##LO(int n, int g, const WalkParams& p, const CxExactParams& e, int grid,   \
+                                   hipStream_t s);                                                        \
+  hipError_t occupancy_cplxexact_##LO(int n, int g, int* blocks_per_cu);
+SUP_DECL_CPLXEXACT(1)
+SUP_DECL_CPLXEXACT(17)
+SUP_DECL_CPLXEXACT(33)
+SUP_DECL_CPLXEXACT(49)
+#undef SUP_DECL_CPLXEXACT
 #define SUP_DECL_CPLXB(LO)                                                                       \
   hipError_t launch_cplxb_##LO(int n, const WalkParams& p, int hbits, int grid, hipStream_t s); \
   hipError_t occupancy_cplxb_##LO(int n, int* blocks_per_cu);
@@ -166,6 +177,13 @@ hipError_t cplx_occupancy(int n, int* blocks_per_cu);
 // p.chunk_out = 4 doubles (re.hi, re.lo, im.hi, im.lo) per wave-chunk.
 hipError_t launch_cplxdd(int n, const WalkParams& p, int grid, hipStream_t s);
 hipError_t cplxdd_occupancy(int n, int* blocks_per_cu);
+
+// Exact complex residue walk (walk_cplxexact.hip), n <=
+// SUP_CPLX_EXACT_MAX_DEVICE_N (larger: hipErrorInvalidValue): p.cols / p.x0 as
+// launch_cplx's, of the doubled matrix; rows multiplied in exact groups of g
+// (1 or 2); e.wave_out = 2 kMaxCxPrimes doubles per wave of the grid.
+hipError_t launch_cplxexact(int n, int g, const WalkParams& p, const CxExactParams& e, int grid, hipStream_t s);
+hipError_t cplxexact_occupancy(int n, int g, int* blocks_per_cu);
 
 // Batched complex walk (walk_cplxb.hip, n <= 32): the wave-chunks of
 // p.chunk_count >> hbits matrices in one queue; global chunk a is chunk

@@ -30,6 +30,12 @@
 // prints "Permanent (double-double): <re_hi> <re_lo> <im_hi> <im_lo>".  Refused
 // with the options --complex is refused with; --complex beside it changes
 // nothing.
+// --complex-exact (no short letter): the same file, whose parts must be
+// integers, through sup_perman_complex_exact (residue walk over (Z/p)[i] and
+// CRT; on the device up to n = SUP_CPLX_EXACT_MAX_DEVICE_N, on -t host threads
+// with -c up to 64); prints "Permanent (exact): <re> <im>", two decimal
+// integers.  Refused with the options --complex is refused with and with
+// --complex-quad; --complex beside it changes nothing.
 #include <getopt.h>
 
 #include <chrono>
@@ -48,7 +54,7 @@ namespace {
 struct Cli {
   bool generic = true, dense = true, approximation = false, gpu = false, cpu = false, grid_graph = false;
   bool rccl = false, verbose = false, compression = false, exact = false, quad = false;
-  bool half_calc = false, half_store = false, complex = false, complex_quad = false, preprocessing_given = false, gpu_num_given = false;
+  bool half_calc = false, half_store = false, complex = false, complex_quad = false, complex_exact = false, preprocessing_given = false, gpu_num_given = false;
   int gpu_num = 2, threads = 16, perman_algo = 1, preprocessing = 0, device = 0, reps = 1;
   double scaling = -1.0;
   long number_of_times = 100000;  // main.cu:338-344 defaults
@@ -137,15 +143,17 @@ int run_approx(const Cli& c) {
 
 // --complex: the complex fp64 walk (sup_perman_complex) of a MatrixMarket
 // `complex` file; same line shape as -q.  --complex-quad: the same file
-// through sup_perman_complex_quad (the walk in double-double).
+// through sup_perman_complex_quad (the walk in double-double).  --complex-exact:
+// through sup_perman_complex_exact (Gaussian integers, exact).
 int run_complex(const Cli& c) {
-  const char* flag = c.complex_quad ? "--complex-quad" : "--complex";
+  const char* flag = c.complex_exact ? "--complex-exact" : c.complex_quad ? "--complex-quad" : "--complex";
   const struct {
     bool on;
     const char* opt;
   } refused[] = {{!c.dense, "-s"},       {c.compression, "-o"},  {c.scaling > 0.0, "-u"},
                  {c.exact, "-E"},        {c.quad, "-q"},         {c.approximation, "-a"},
-                 {!c.generic, "-b"},     {c.grid_graph, "-i"},   {c.preprocessing_given, "-r"}};
+                 {!c.generic, "-b"},     {c.grid_graph, "-i"},   {c.preprocessing_given, "-r"},
+                 {c.complex_exact && c.complex_quad, "--complex-quad"}};
   for (const auto& r : refused)
     if (r.on) {
       std::fprintf(stderr, "perman: %s does not combine with %s\n", flag, r.opt);
@@ -161,16 +169,25 @@ int run_complex(const Cli& c) {
   o.threads = c.threads;
   double re = 0.0, im = 0.0;
   double q[4] = {0.0, 0.0, 0.0, 0.0};  // --complex-quad: re_hi, re_lo, im_hi, im_lo
+  char xre[640] = "0", xim[640] = "0";   // --complex-exact: decimal integers
   sup_stats st;
   int rc = SUP_OK;
   const auto t0 = std::chrono::steady_clock::now();
   for (int rep = 0; rep < c.reps && rc == SUP_OK; ++rep)
-    rc = c.complex_quad ? sup_perman_complex_quad(mat, n, &o, c.gpu ? 0 : 1, q, &st)
-                        : sup_perman_complex(mat, n, &o, c.gpu ? 0 : 1, &re, &im, &st);
+    rc = c.complex_exact  ? sup_perman_complex_exact(mat, n, &o, c.gpu ? 0 : 1, xre, xim, sizeof(xre), &st)
+         : c.complex_quad ? sup_perman_complex_quad(mat, n, &o, c.gpu ? 0 : 1, q, &st)
+                          : sup_perman_complex(mat, n, &o, c.gpu ? 0 : 1, &re, &im, &st);
   const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / (double)c.reps;
   sup_free(mat);
-  if (rc != SUP_OK) return fail(c.complex_quad ? "complex double-double permanent" : "complex permanent");
-  if (c.complex_quad) {
+  if (rc != SUP_OK)
+    return fail(c.complex_exact  ? "exact complex permanent"
+                : c.complex_quad ? "complex double-double permanent"
+                                 : "complex permanent");
+  if (c.complex_exact) {
+    std::cout << "Result: " << (c.gpu ? "gpu_perman64_complex_exact" : "cpu_perman64_complex_exact") << " "
+              << std::strtod(xre, nullptr) << " " << std::strtod(xim, nullptr) << " in " << sec << std::endl;
+    std::printf("Permanent (exact): %s %s\n", xre, xim);
+  } else if (c.complex_quad) {
     std::cout << "Result: " << (c.gpu ? "gpu_perman64_complex_quad" : "cpu_perman64_complex_quad") << " " << q[0]
               << " " << q[2] << " in " << sec << std::endl;
     std::printf("Permanent (double-double): %.17e %.17e %.17e %.17e\n", q[0], q[1], q[2], q[3]);
@@ -207,6 +224,7 @@ int main(int argc, char** argv) {
                                         {"gridMultip", 1, NULL, 'e'},    {"checkpoint", 1, NULL, 'C'},
                                         {"complex", 0, NULL, 1000},
                                         {"complex-quad", 0, NULL, 1001},
+                                        {"complex-exact", 0, NULL, 1002},
                                         {NULL, 0, NULL, 0}};
   int opt;
   auto need_arg = [&](char o) -> bool {
@@ -244,6 +262,7 @@ int main(int argc, char** argv) {
       case 'q': c.quad = true; break;
       case 1000: c.complex = true; break;
       case 1001: c.complex_quad = true; break;
+      case 1002: c.complex_exact = true; break;
       case 'v': c.verbose = true; break;
       // v2 flags (revised_perman/main.cpp:1431-1460): -w stores the matrix in
       // single precision (the permanent of the float-rounded entries); -h asks
@@ -271,7 +290,7 @@ int main(int argc, char** argv) {
   }
   for (int i = optind; i < argc; ++i) std::printf("Non-option argument %s\n", argv[i]);
   if (!c.cpu && !c.gpu) c.gpu = true;  // main.cu:482-484
-  if (c.complex || c.complex_quad) return run_complex(c);
+  if (c.complex || c.complex_quad || c.complex_exact) return run_complex(c);
   if (c.grid_graph || c.approximation) return run_approx(c);
 
   void* mat = nullptr;

@@ -314,6 +314,20 @@ hipError_t cplxdd_occupancy(int n, int* blocks_per_cu) {
   SUP_DISPATCH_CPLXDD(occupancy, n, blocks_per_cu)
 }
 
+// walk_cplxexact.hip: four ranges, the last 49..SUP_CPLX_EXACT_MAX_DEVICE_N
+static_assert(SUP_CPLX_EXACT_MAX_DEVICE_N > 48 && SUP_CPLX_EXACT_MAX_DEVICE_N <= 64,
+              "walk_cplxexact's fourth range is 49..SUP_CPLX_EXACT_MAX_DEVICE_N (Makefile)");
+
+hipError_t launch_cplxexact(int n, int g, const WalkParams& p, const CxExactParams& e, int grid, hipStream_t s) {
+  if (n < 1 || n > SUP_CPLX_EXACT_MAX_DEVICE_N) return hipErrorInvalidValue;
+  SUP_DISPATCH(cplxexact, launch, n, g, p, e, grid, s)
+}
+
+hipError_t cplxexact_occupancy(int n, int g, int* blocks_per_cu) {
+  if (n < 1 || n > SUP_CPLX_EXACT_MAX_DEVICE_N) return hipErrorInvalidValue;
+  SUP_DISPATCH(cplxexact, occupancy, n, g, blocks_per_cu)
+}
+
 hipError_t exact_occupancy(int n, int g, int* blocks_per_cu) {
   if (n < 1 || n > 64) return hipErrorInvalidValue;
   SUP_DISPATCH(exact, occupancy, n, g, blocks_per_cu)

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SUP_ABI_VERSION 19  /* 19: sup_perman_complex_exact, sup_perman_complex_exact_range, SUP_CPLX_EXACT_MAX_DEVICE_N; 18: sup_perman_complex_quad, sup_perman_complex_quad_range, SUP_CPLX_QUAD_MAX_DEVICE_N; 17:sup_perman_complex_fock_minors, sup_perman_complex_fock_minors_plan, sup_boson_sample_fock; 16: sup_plan_census; 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
+#define SUP_ABI_VERSION 20  /* 20: sup_hafnian_complex, sup_loop_hafnian_complex, sup_hafnian_complex_plan; 19: sup_perman_complex_exact, sup_perman_complex_exact_range, SUP_CPLX_EXACT_MAX_DEVICE_N; 18: sup_perman_complex_quad, sup_perman_complex_quad_range, SUP_CPLX_QUAD_MAX_DEVICE_N; 17:sup_perman_complex_fock_minors, sup_perman_complex_fock_minors_plan, sup_boson_sample_fock; 16: sup_plan_census; 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SUP_OK            0
@@ -690,6 +690,43 @@ int sup_perman_complex_fock_minors_plan(const int32_t* cols, int n, uint64_t cou
 int sup_boson_sample_fock(const double* U, int M, const int32_t* inputs, int n, uint64_t nsamples, uint64_t seed,
                           const sup_opts* o, int on_cpu, int32_t* out /* nsamples x n, ascending modes */,
                           sup_stats* st);
+
+/* Hafnians and loop hafnians with repeats (ABI 20): the amplitudes of Gaussian
+ * boson sampling.  A is M x M complex (row-major, interleaved re, im) and
+ * symmetric bit for bit; matrix k is the n x n gather A[idx[k n + i]][idx[k n
+ * + j]], 1 <= n <= 64, the list may repeat (one index per detected photon).
+ * With the K distinct values of the list (multiplicities s_k, order of first
+ * appearance; two copies of one value may pair: the diagonal of A counts), one
+ * copy of the rarest group held (s'_k) and h_k = s_k / 2 - v_k,
+ *   haf = 2 / (n/2)!  sum_{0 <= v_k <= s'_k} (-1)^(sum v) prod C(s'_k, v_k) (q(v) / 2)^(n/2)
+ *   q(v) = sum_kl h_k A_kl h_l
+ * has T = prod (s'_k + 1) terms (2^(n-1) without repeats); odd n
+ * gives exactly 0 and walks nothing.  The layout (walk digits, Tw, H) is
+ * sup_perman_complex_fock's rule on the multiplicity vector.  out[2k],
+ * out[2k + 1] = Re, Im of result k: a function of (A, mu, idx[k]) only,
+ * bit-identical on the device (walk_haf.hip), on any device count (o->gpu_num
+ * devices take contiguous ranges of matrices), for any slab size and on host
+ * threads (on_cpu = 1).  It is not bit-identical to a permanent entry on the
+ * bipartite embedding.  Without repeats the cost is 2^(n-1) states: the entry
+ * is meant for patterns with collisions and for small orders.
+ * Errors, all before any device work: a null pointer, n outside [1, 64], an
+ * index outside [0, M), a pair A[i][j], A[j][i] that differs: SUP_EINVAL with a
+ * message naming the place; a matrix of more than 2^24 wave-chunks:
+ * SUP_EUNSUPPORTED; no device with on_cpu = 0: SUP_ENODEV (no CPU fallback).
+ * st: leaves = count, gray_steps = count 2^(n-1) (nominal), visited_steps =
+ * sum_k T_k, kernel_ms, wall_ms, devices_used, grid, est_ops_per_step = the op
+ * census of DESIGN.md 8h (the T-weighted mean over the matrices). */
+int sup_hafnian_complex(const double* A, int M, const int32_t* idx, int n, uint64_t count, const sup_opts* o,
+                        int on_cpu, double* out, sup_stats* st);
+/* The loop hafnian of the same gathers: mu (M complex, interleaved) replaces
+ * the diagonal on self-loops, mu_k = mu[idx value k].  With r(v) = sum_k mu_k h_k
+ *   lhaf = 2 sum_v (-1)^(sum v) prod C(s'_k, v_k) sum_{j <= n/2} (q/2)^j / j! r^(n-2j) / (n-2j)!
+ * for even and odd n.  Arguments, errors, bits and stats as sup_hafnian_complex. */
+int sup_loop_hafnian_complex(const double* A, int M, const double* mu, const int32_t* idx, int n, uint64_t count,
+                             const sup_opts* o, int on_cpu, double* out, sup_stats* st);
+/* The terms T of each matrix's sum, host only (no device).  terms may be NULL.
+ * A null list or n outside [1, 64]: SUP_EINVAL.  Indices are only compared. */
+int sup_hafnian_complex_plan(const int32_t* idx, int n, uint64_t count, uint64_t* terms);
 
 /* Nijenhuis-Wilf prologue (gpu_exact_dense.cu:642-652): x0[j] = a[j][n-1] - rowsum_j/2,
  * p0 = prod x0.  Host-only helper, exported for the test harness. */

@@ -21,7 +21,8 @@ from ._lib import (KERNEL_DENSE, KERNEL_SKIPPER, KERNEL_SPARYSER, LEAF_FN, SCHED
 
 __all__ = [
     "perman", "perman_cpu", "perman_exact", "perman_exact_range", "perman_quad", "perman_quad_range", "perman_complex", "perman_complex_range", "perman_complex_quad", "perman_complex_quad_range", "COMPLEX_QUAD_MAX_DEVICE_N", "perman_complex_exact", "perman_complex_exact_range", "COMPLEX_EXACT_MAX_DEVICE_N", "perman_complex_batch", "perman_complex_submatrices", "perman_complex_fock", "perman_complex_fock_plan", "perman_complex_fock_minors", "perman_complex_fock_minors_submatrices",
-           "perman_complex_fock_minors_plan", "perman_complex_minors", "perman_complex_minors_submatrices", "perman_complex_minors_range", "boson_sample", "read_mtx_complex", "partial", "perman_shard", "plan_info", "plan_census", "CENSUS_CLASSES", "plan_key", "prepare", "read_matrix", "read_mtx", "sort_order",
+           "hafnian", "loop_hafnian", "hafnian_repeated", "hafnian_batch", "hafnian_plan",
+           "perman_complex_fock_minors_plan","perman_complex_minors", "perman_complex_minors_submatrices", "perman_complex_minors_range", "boson_sample", "read_mtx_complex", "partial", "perman_shard", "plan_info", "plan_census", "CENSUS_CLASSES", "plan_key", "prepare", "read_matrix", "read_mtx", "sort_order",
     "skip_order", "compress", "decompose", "perman_reduced", "approx", "grid_graph", "ALGOS_APPROX",
     "nw_start", "device_count", "rccl_devices", "layout", "ShardCall", "SupError", "ALGOS_DENSE", "ALGOS_SPARSE",
     "gpu_perman64_xshared_coalescing_mshared",
@@ -712,6 +713,92 @@ def perman_complex_fock_minors_plan(cols):
     terms = np.zeros(max(count, 1), np.uint64)
     _lib.check(_lib.load().sup_perman_complex_fock_minors_plan(c32.ctypes.data, q + 1, count, terms.ctypes.data),
                "perman_complex_fock_minors_plan")
+    return int(terms[0]) if single else terms[:count].copy()
+
+
+def _haf_lists(idx):
+    """idx of shape [n] or [count, n] as contiguous int32 [count, n]; single:
+    the list had shape [n]."""
+    ix = np.asarray(idx)
+    single = ix.ndim == 1
+    if single:
+        ix = ix[None, :]
+    if ix.ndim != 2:
+        raise ValueError(f"idx must have shape [n] or [count, n], got {np.shape(idx)}")
+    if ix.size and not np.issubdtype(ix.dtype, np.integer):
+        raise ValueError(f"idx must be an integer array, got dtype {ix.dtype}")
+    if ix.size and (ix.min() < -2**31 or ix.max() >= 2**31):
+        raise ValueError("idx holds an index outside the 32-bit range")
+    count, n = ix.shape
+    if not 1 <= n <= 64:
+        raise ValueError(f"n = {n} outside [1, 64] (64-bit Gray index)")
+    i32 = np.ascontiguousarray(ix, dtype=np.int32) if count else np.zeros(1, np.int32)
+    return i32, count, n, single
+
+
+def hafnian_batch(A, idx, mu=None, loop: bool = False, gpu_num: int = 1, device_id: int = 0, cpu: bool = False,
+                  threads: int = 16, return_stats: bool = False):
+    """The hafnians (``loop=True``: the loop hafnians) of the gathers
+    ``A[np.ix_(idx[k], idx[k])]`` of one complex symmetric matrix A
+    (sup_hafnian_complex, sup_loop_hafnian_complex): the lists may repeat, one
+    index per detected photon, and the sum runs over the multiplicity vectors,
+    T = prod (s'_k + 1) terms instead of 2^(n-1) (the hafnian walk
+    walk_haf.hip, or (cpu=True) its host twin, bit-identical).  ``mu``
+    (length M, default the diagonal of A) replaces the diagonal on self-loops
+    of the loop form.  A list of shape [n] gives one Python complex, of shape
+    [count, n] a complex128 array of shape [count].  Without repeats the cost
+    is 2^(n-1) states: this entry is for patterns with collisions and small
+    orders."""
+    a = np.ascontiguousarray(np.asarray(A, dtype=np.complex128))
+    if a.ndim != 2 or a.shape[0] != a.shape[1] or a.shape[0] < 1:
+        raise ValueError(f"expected a non-empty square matrix A, got shape {a.shape}")
+    i32, count, n, single = _haf_lists(idx)
+    lib = _lib.load()
+    o = _opts(gpu_num=gpu_num, device_id=device_id, threads=threads)
+    out, st = np.zeros(2 * max(count, 1)), SupStats()
+    if loop:
+        m = np.ascontiguousarray(np.diag(a) if mu is None else np.asarray(mu, dtype=np.complex128))
+        if m.shape != (a.shape[0],):
+            raise ValueError(f"mu must have shape [{a.shape[0]}], got {m.shape}")
+        rc = lib.sup_loop_hafnian_complex(a.ctypes.data, a.shape[0], m.ctypes.data, i32.ctypes.data, n, count,
+                                          C.byref(o), int(bool(cpu)), out.ctypes.data, C.byref(st))
+    else:
+        rc = lib.sup_hafnian_complex(a.ctypes.data, a.shape[0], i32.ctypes.data, n, count, C.byref(o),
+                                     int(bool(cpu)), out.ctypes.data, C.byref(st))
+    _lib.check(rc, "loop_hafnian" if loop else "hafnian")
+    v = _batch_result(out, count)
+    v = complex(v[0]) if single else v
+    return (v, st.as_dict()) if return_stats else v
+
+
+def hafnian(A, **kw):
+    """The hafnian of the whole complex symmetric matrix A (``hafnian_batch``
+    with idx = 0..n-1; n <= 64, 2^(n-1) states)."""
+    return hafnian_batch(A, np.arange(np.shape(A)[0]), **kw)
+
+
+def loop_hafnian(A, mu=None, **kw):
+    """The loop hafnian of the whole matrix A; ``mu`` defaults to its diagonal."""
+    return hafnian_batch(A, np.arange(np.shape(A)[0]), mu=mu, loop=True, **kw)
+
+
+def hafnian_repeated(A, rpt, mu=None, loop: bool = False, **kw):
+    """The (loop) hafnian of A with mode k taken ``rpt[k]`` times (zeros
+    allowed): ``hafnian_batch`` on the list that repeats k rpt[k] times."""
+    r = np.asarray(rpt)
+    if (r.ndim != 1 or r.shape[0] != np.shape(A)[0] or (r.size and not np.issubdtype(r.dtype, np.integer))
+            or (r < 0).any()):
+        raise ValueError(f"rpt must hold one non-negative integer per mode of A, got {rpt!r}")
+    return hafnian_batch(A, np.repeat(np.arange(r.shape[0]), r), mu=mu, loop=loop, **kw)
+
+
+def hafnian_plan(idx):
+    """The terms T ``hafnian_batch`` walks for these lists
+    (sup_hafnian_complex_plan, host only): an int for a list of shape [n], a
+    uint64 array of shape [count] for [count, n]."""
+    i32, count, n, single = _haf_lists(idx)
+    terms = np.zeros(max(count, 1), np.uint64)
+    _lib.check(_lib.load().sup_hafnian_complex_plan(i32.ctypes.data, n, count, terms.ctypes.data), "hafnian_plan")
     return int(terms[0]) if single else terms[:count].copy()
 
 

@@ -613,6 +613,47 @@ int sup_perman_complex_fock_plan(const int32_t* rows, const int32_t* cols, int n
   return cplx_fock_plan(rows, cols, n, count, terms, side);
 }
 
+static int hafnian_entry(const HafIn& in, int n, uint64_t count, const sup_opts* o_in, int on_cpu, double* out,
+                         sup_stats* st) {
+  auto t0 = std::chrono::steady_clock::now();
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  HafInfo hi;
+  if (int rc = hafnian_complex(in, n, count, o, on_cpu != 0, out, &hi)) return rc;
+  if (st) {
+    std::memset(st, 0, sizeof(*st));
+    st->kernel_ms = hi.kernel_ms;
+    st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    st->gray_steps = count << (n - 1);  // nominal: the sum without repeats
+    st->visited_steps = hi.terms;
+    st->devices_used = hi.devices;
+    st->grid = hi.grid;
+    st->walk_kind = (int)kWalkDense;
+    st->leaves = (int)std::min<uint64_t>(count, 0x7fffffffu);
+    st->est_ops_per_step = hi.ops;
+  }
+  return SUP_OK;
+}
+
+int sup_hafnian_complex(const double* A, int M, const int32_t* idx, int n, uint64_t count, const sup_opts* o,
+                        int on_cpu, double* out, sup_stats* st) {
+  HafIn in;
+  in.A = A, in.M = M, in.idx = idx;
+  return hafnian_entry(in, n, count, o, on_cpu, out, st);
+}
+
+int sup_loop_hafnian_complex(const double* A, int M, const double* mu, const int32_t* idx, int n, uint64_t count,
+                             const sup_opts* o, int on_cpu, double* out, sup_stats* st) {
+  HafIn in;
+  in.A = A, in.M = M, in.mu = mu, in.idx = idx, in.loop = true;
+  return hafnian_entry(in, n, count, o, on_cpu, out, st);
+}
+
+int sup_hafnian_complex_plan(const int32_t* idx, int n, uint64_t count, uint64_t* terms) {
+  return hafnian_plan(idx, n, count, terms);
+}
+
 // sup_stats of a minors call: the batch entry's, with the one-walk step cost.
 static void fill_minors_stats(sup_stats* st, const CplxInfo& ci, int n, uint64_t outputs, uint64_t steps,
                               double wall_ms) {

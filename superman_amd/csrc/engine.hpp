@@ -713,4 +713,50 @@ int cplx_fock_minors(const CplxBatchIn& in, int n, uint64_t count, const sup_opt
 // Per matrix the terms T of that sum (cols: count x (n-1)).  Host only.
 int cplx_fock_minors_plan(const int32_t* cols, int n, uint64_t count, uint64_t* terms);
 
+// ---- hafnians and loop hafnians with repeats (hafnian.cpp; walk_haf.hip, haf.hpp) ----
+// Matrix k is the symmetric gather A[idx[k n + i]][idx[k n + j]] of the M x M
+// complex matrix A (row-major interleaved); mu (M complex) replaces the
+// diagonal on self-loops in the loop form and is null otherwise.
+struct HafIn {
+  const double* A = nullptr;
+  int M = 0;
+  const double* mu = nullptr;
+  const int32_t* idx = nullptr;
+  bool loop = false;
+};
+// A slab of matrices of order n as the walk reads it (haf.hpp), built on the
+// host by hafnian.cpp.
+struct HafSlab {
+  int n = 0;
+  bool loop = false;
+  uint64_t tab_doubles = 0;
+  std::vector<double> tabs;  // filled for the host twin only: the device writes its own
+  std::vector<HafStep> prog;
+  std::vector<HafDigit> dig;
+  std::vector<int32_t> grp;
+  std::vector<HafMat> mats;
+  std::vector<FockChunk> chunks;
+  std::vector<double> coef;  // loop form: 1 / (j! (n - 2j)!)
+  double div = 1.0;          // m! (hafnian) or 1 (loop hafnian)
+};
+// Prepares (tables from in.A, in.mu and the slab's groups), walks and folds
+// slab S on device `dev`: out[2k], out[2k + 1] = the (loop) hafnian of its
+// matrix k, bit-identical to the host twin.  *kernel_ms: prepare + walk + fold
+// kernel time; *grid: blocks of the walk launch.
+int run_hafnian(int dev, const HafSlab& S, const HafIn& in, double* out, double* kernel_ms, int* grid = nullptr);
+struct HafInfo {
+  double kernel_ms = 0.0;
+  int devices = 0, grid = 0;
+  uint64_t terms = 0;  // sum over the matrices of T
+  double ops = 0.0;    // the T-weighted mean of haf_ops over the matrices
+};
+// out[2k], out[2k + 1] = the hafnian (in.loop: the loop hafnian) of matrix k,
+// k < count (sup_hafnian_complex, sup_loop_hafnian_complex).  Arguments,
+// symmetry and indices are checked before any work; odd n without loop writes
+// zeros and walks nothing.
+int hafnian_complex(const HafIn& in, int n, uint64_t count, const sup_opts& o, bool on_cpu, double* out,
+                    HafInfo* info);
+// Per matrix the terms T of its sum (sup_hafnian_complex_plan).  Host only.
+int hafnian_plan(const int32_t* idx, int n, uint64_t count, uint64_t* terms);
+
 }  // namespace sup

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "cplx_fock.hpp"
+#include "haf.hpp"
 #include "cxexact.hpp"
 #include "walk_batch.hpp"
 #include "walk_params.hpp"
@@ -249,6 +250,19 @@ hipError_t cplx_fock_minors_occupancy(int n, int* blocks_per_cu);
 // partials at parts + 2 (n mats[k].chunk0 + j mats[k].chunks) (cplx_fock.hip).
 hipError_t launch_cplx_fock_minors_fold(const double* parts, const FockMat* mats, uint64_t K, int n, double* out,
                                         hipStream_t s);
+
+// Hafnian / loop hafnian walk (walk_haf.hip, n <= 64, one kernel per form): the
+// wave-chunks of a slab of matrices in one queue, described by HafParams
+// (haf.hpp).
+hipError_t launch_haf(bool loop, const HafParams& p, int grid, hipStream_t s);
+hipError_t haf_occupancy(bool loop, int* blocks_per_cu);
+// The tables of the K matrices of a slab (haf.hpp haf_entry), written from A
+// (M x M), mu (M, or null for the plain hafnian) and the groups in grp.
+hipError_t launch_haf_prepare(const double* A, int M, const double* mu, const int32_t* grp, const HafMat* mats,
+                              uint64_t K, double* tabs, hipStream_t s);
+// out[2k], out[2k + 1] = 2 x fock_fold over matrix k's partials, divided by div.
+hipError_t launch_haf_fold(const double* parts, const HafMat* mats, uint64_t K, double div, double* out,
+                           hipStream_t s);
 
 // Fixed-order pairwise reduction of `count` doubles into *out (64-way passes,
 // zero padded; mirrored by oracle/oracle.c orc_pairwise_reduce).  `scratch`

@@ -36,6 +36,12 @@
 // with -c up to 64); prints "Permanent (exact): <re> <im>", two decimal
 // integers.  Refused with the options --complex is refused with and with
 // --complex-quad; --complex beside it changes nothing.
+// --hafnian [--loop] [--rpt 2,0,1,...] (no short letters): the hafnian (--loop:
+// the loop hafnian, mu = the diagonal) of the same kind of file, which must be
+// symmetric, through sup_hafnian_complex / sup_loop_hafnian_complex; --rpt
+// takes mode k rpt[k] times (default: every mode once).  -g the device walk,
+// -c the host threads; prints "Hafnian: <re> <im>".  Refused with the options
+// --complex is refused with and with the --complex flags.
 #include <getopt.h>
 
 #include <chrono>
@@ -55,13 +61,14 @@ struct Cli {
   bool generic = true, dense = true, approximation = false, gpu = false, cpu = false, grid_graph = false;
   bool rccl = false, verbose = false, compression = false, exact = false, quad = false;
   bool half_calc = false, half_store = false, complex = false, complex_quad = false, complex_exact = false, preprocessing_given = false, gpu_num_given = false;
+  bool hafnian = false, loop = false;
   int gpu_num = 2, threads = 16, perman_algo = 1, preprocessing = 0, device = 0, reps = 1;
   double scaling = -1.0;
   long number_of_times = 100000;  // main.cu:338-344 defaults
   int scale_intervals = 4, scale_times = 5, gridm = 36, gridn = 36;
   unsigned long long seed = 1;
   int jit = 0;
-  std::string filename, checkpoint;
+  std::string filename, checkpoint, rpt;
 };
 
 int fail(const char* what) {
@@ -202,6 +209,72 @@ int run_complex(const Cli& c) {
   return 0;
 }
 
+// --hafnian: sup_hafnian_complex / sup_loop_hafnian_complex of a symmetric
+// MatrixMarket `complex` file; the line shape follows --complex.
+int run_hafnian_cli(const Cli& c) {
+  const struct {
+    bool on;
+    const char* opt;
+  } refused[] = {{!c.dense, "-s"},       {c.compression, "-o"},    {c.scaling > 0.0, "-u"},
+                 {c.exact, "-E"},        {c.quad, "-q"},           {c.approximation, "-a"},
+                 {!c.generic, "-b"},     {c.grid_graph, "-i"},     {c.preprocessing_given, "-r"},
+                 {c.complex, "--complex"}, {c.complex_quad, "--complex-quad"}, {c.complex_exact, "--complex-exact"}};
+  for (const auto& r : refused)
+    if (r.on) {
+      std::fprintf(stderr, "perman: --hafnian does not combine with %s\n", r.opt);
+      return 1;
+    }
+  double* mat = nullptr;
+  int M = 0, nnz = 0;
+  if (sup_read_mtx_complex(c.filename.c_str(), &mat, &M, &nnz) != SUP_OK) return fail("reading complex matrix");
+  std::vector<int32_t> idx;
+  if (c.rpt.empty()) {
+    for (int k = 0; k < M; ++k) idx.push_back(k);
+  } else {
+    int k = 0;
+    for (const char* p = c.rpt.c_str(); *p; ++k) {
+      char* end = nullptr;
+      const long r = std::strtol(p, &end, 10);
+      if (end == p || r < 0 || (*end && *end != ',') || k >= M || idx.size() + (size_t)r > 64) {
+        std::fprintf(stderr, "perman: --rpt takes at most %d non-negative counts with a sum in [1, 64]\n", M);
+        sup_free(mat);
+        return 1;
+      }
+      idx.insert(idx.end(), (size_t)r, k);
+      p = *end ? end + 1 : end;
+    }
+  }
+  if (idx.empty() || idx.size() > 64) {
+    std::fprintf(stderr, "perman: --hafnian needs 1 to 64 indices (got %zu)\n", idx.size());
+    sup_free(mat);
+    return 1;
+  }
+  std::vector<double> mu((size_t)2 * M);
+  for (int k = 0; k < M; ++k) mu[2 * k] = mat[2 * ((size_t)k * M + k)], mu[2 * k + 1] = mat[2 * ((size_t)k * M + k) + 1];
+  sup_opts o;
+  sup_opts_init(&o);
+  o.gpu_num = 1;
+  o.device_id = c.device;
+  o.threads = c.threads;
+  double out[2] = {0.0, 0.0};
+  sup_stats st;
+  int rc = SUP_OK;
+  const auto t0 = std::chrono::steady_clock::now();
+  for (int rep = 0; rep < c.reps && rc == SUP_OK; ++rep)
+    rc = c.loop ? sup_loop_hafnian_complex(mat, M, mu.data(), idx.data(), (int)idx.size(), 1, &o, c.gpu ? 0 : 1, out, &st)
+                : sup_hafnian_complex(mat, M, idx.data(), (int)idx.size(), 1, &o, c.gpu ? 0 : 1, out, &st);
+  const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / (double)c.reps;
+  sup_free(mat);
+  if (rc != SUP_OK) return fail(c.loop ? "loop hafnian" : "hafnian");
+  std::cout << "Result: " << (c.gpu ? "gpu_" : "cpu_") << (c.loop ? "loop_hafnian64_complex" : "hafnian64_complex") << " "
+            << out[0] << " " << out[1] << " in " << sec << std::endl;
+  std::printf("Hafnian: %.17e %.17e\n", out[0], out[1]);
+  if (c.verbose)
+    std::printf("Stats: devices %d kernel_ms %.3f wall_ms %.3f terms %llu grid %d\n", st.devices_used, st.kernel_ms,
+                st.wall_ms, (unsigned long long)st.visited_steps, st.grid);
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -225,6 +298,9 @@ int main(int argc, char** argv) {
                                         {"complex", 0, NULL, 1000},
                                         {"complex-quad", 0, NULL, 1001},
                                         {"complex-exact", 0, NULL, 1002},
+                                        {"hafnian", 0, NULL, 1003},
+                                        {"loop", 0, NULL, 1004},
+                                        {"rpt", 1, NULL, 1005},
                                         {NULL, 0, NULL, 0}};
   int opt;
   auto need_arg = [&](char o) -> bool {
@@ -263,6 +339,9 @@ int main(int argc, char** argv) {
       case 1000: c.complex = true; break;
       case 1001: c.complex_quad = true; break;
       case 1002: c.complex_exact = true; break;
+      case 1003: c.hafnian = true; break;
+      case 1004: c.loop = true; break;
+      case 1005: c.rpt = optarg; break;
       case 'v': c.verbose = true; break;
       // v2 flags (revised_perman/main.cpp:1431-1460): -w stores the matrix in
       // single precision (the permanent of the float-rounded entries); -h asks
@@ -290,6 +369,11 @@ int main(int argc, char** argv) {
   }
   for (int i = optind; i < argc; ++i) std::printf("Non-option argument %s\n", argv[i]);
   if (!c.cpu && !c.gpu) c.gpu = true;  // main.cu:482-484
+  if (c.hafnian) return run_hafnian_cli(c);
+  if (c.loop || !c.rpt.empty()) {
+    std::fprintf(stderr, "perman: --loop and --rpt go with --hafnian\n");
+    return 1;
+  }
   if (c.complex || c.complex_quad || c.complex_exact) return run_complex(c);
   if (c.grid_graph || c.approximation) return run_approx(c);
 

@@ -684,6 +684,9 @@ int run_range(int dev, const Plan& P, uint64_t c0, uint64_t c1, bool want_visite
   // walked states per chunk: SkipPer's jumps, the segmented walk's chunk skip
   // (only where the walk leaves rows untouched)
   const bool visited = want_visited && (P.kind == kWalkSkip || (seg && P.outer_tree.tail_hi > P.outer_tree.tail_lo));
+  // ... and the prefix-blocked walk's chunk ends: the kernel counts the chunks
+  // it ended (kernels.hpp kChunkEndWords), the rest were walked whole
+  const bool ends = want_visited && P.kind == kWalkSparse && !P.lds && P.chunk_ends;
   // the plan's tables: uploaded unless this device already holds them (same
   // cached plan, buffers not reallocated) — repeated calls on one matrix
   // (bench steps, -p6 items, reduction leaves) skip five H2D copies
@@ -697,6 +700,14 @@ int run_range(int dev, const Plan& P, uint64_t c0, uint64_t c1, bool want_visite
   const bool fused = fold_fused() && !P.lds &&
                      (seg || P.kind == kWalkDense || P.kind == kWalkSparse || P.kind == kWalkSkip);
   if (fused && (rc = ensure_fold_counters(c, count))) return rc;
+  // the chunk-end words, behind the per-chunk words the unfused chunk_store writes (walk_sparse.hip)
+  unsigned* end_words = nullptr;
+  if (ends) {
+    const size_t first = fused ? 0 : (size_t)count;
+    if ((rc = ensure(c->d_visited, c->visited_cap, first + kChunkEndWords))) return rc;
+    end_words = c->d_visited + first;
+    SUP_HIP(hipMemsetAsync(end_words, 0, kChunkEndWords * sizeof(unsigned), s));
+  }
   const int qh = fused ? c->head : 0;
   unsigned* head = c->d_counter + 16 * qh;
   // the queue head: zeroed by the previous run_range's reduction, else here
@@ -717,7 +728,7 @@ int run_range(int dev, const Plan& P, uint64_t c0, uint64_t c1, bool want_visite
   p.rowmask = c->d_rowmask;
   p.umask = P.kind == kWalkSparse ? P.chunk_ends : P.umask;  // walk_sparse: its chunk-end rows
   p.chunk_out = c->d_chunk;
-  p.visited = visited && !fused ? c->d_visited : nullptr;
+  p.visited = (visited && !fused) || ends ? c->d_visited : nullptr;
   p.tail_group = geo.tail_group;
   p.tail_begin = geo.tail_begin;
   p.tail_ticket = geo.tail_ticket;
@@ -748,6 +759,11 @@ int run_range(int dev, const Plan& P, uint64_t c0, uint64_t c1, bool want_visite
   SUP_HIP(hipEventRecord(ev.second, s));
   if (defer) c->tally.commit();
   if ((rc = queue_result_copies(c, rp, count, head, slot))) return rc;
+  unsigned long long* esum = reinterpret_cast<unsigned long long*>(c->h_result + 3);  // (beside the visited sum)
+  if (ends) {
+    SUP_HIP(launch_sum_visited(end_words, kChunkEndWords, reinterpret_cast<unsigned long long*>(c->d_result + 3), s));
+    SUP_HIP(hipMemcpyAsync(esum, c->d_result + 3, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  }
 
   // spin on the flag only where the walk is predicted to end within the spin
   // window (cost model on this device's CUs; a longer walk blocks in the
@@ -756,7 +772,7 @@ int run_range(int dev, const Plan& P, uint64_t c0, uint64_t c1, bool want_visite
                               (256.0 / std::max(1, c->cus));
   const bool seen = rp.flagged && predicted_ms <= kFlagSpinMs &&
                     (p.fold_sys ? wait_result(c->h_result) : wait_flag(c->h_flag, rp.seq));
-  if (!seen) SUP_HIP(hipStreamSynchronize(s));
+  if (!seen || ends) SUP_HIP(hipStreamSynchronize(s));  // (the ended chunks' count follows the result)
   if (fused) {  // the final fold zeroed the other head
     c->head_zero[qh ^ 1] = true;
     c->head = qh ^ 1;
@@ -772,7 +788,8 @@ int run_range(int dev, const Plan& P, uint64_t c0, uint64_t c1, bool want_visite
   r.grid = (int)geo.grid;
   if (p.trace && (rc = trace_write(trace_path, p.trace, count, geo, resident * wpb, ms))) return rc;
   const unsigned long long* vsum = reinterpret_cast<const unsigned long long*>(c->h_result + 2);
-  r.visited = visited ? (uint64_t)*vsum * (uint64_t)(1ull << P.lay.L) : count << (P.lay.L + P.lay.m);
+  r.visited = visited ? (uint64_t)*vsum * (uint64_t)(1ull << P.lay.L)
+                      : (count - (ends ? (uint64_t)*esum : 0)) << (P.lay.L + P.lay.m);
   return SUP_OK;
 }
 

@@ -293,7 +293,8 @@ int plan_for_shared(const double* A, int n, sup_kernel kernel, const Layout& lay
 struct RangeResult {
   double partial = 0.0;     // pairwise sum over the range's wave-chunks
   double kernel_ms = 0.0;   // walk kernel device time (hipEvents on the launch stream)
-  uint64_t visited = 0;     // evaluated products (lanes * steps), skipper only
+  uint64_t visited = 0;     // evaluated products (lanes * steps): below the nominal count where the skipper or
+                            // the segmented walk jumped, or the prefix-blocked walk ended chunks
   int grid = 0;
   double compile_ms = 0.0;  // segmented walk: hiprtc compile time spent by this call
 };

@@ -2213,8 +2213,12 @@ int build_seg(Plan& P, int fixed_budget, int fixed_hi) {
   // `out`: SUP_OK, or SUP_EHIP when no budget's kernel is acceptable.
   auto ladder = [&](int hi, Plan& out) -> int {
     // the ladder of budgets, one candidate plan per budget (host threads)
+    // (from kRegs3 + 12: the dense n = 57 pattern of tests/test_gpu_fp64_range.py
+    // in matrix column order with 6 walk bits spills inside the loop at 110 and
+    // above and compiles without scratch at 102; until then the ladder began at
+    // kRegs3 + 20 and that request had no segmented plan)
     std::vector<int> budgets;
-    for (int b2 = kRegs3 + 20; b2 <= kRegsMax + 60; b2 += 8) budgets.push_back(b2);
+    for (int b2 = kRegs3 + 12; b2 <= kRegsMax + 60; b2 += 8) budgets.push_back(b2);
     std::vector<Plan> cand(budgets.size(), P);
     parallel_tasks(budgets.size(), [&](size_t i) { finish(cand[i], budgets[i], hi); });
     // distinct kernels in budget order

@@ -277,6 +277,12 @@ hipError_t launch_pairwise_reduce(const double* in, uint64_t count, double* scra
 uint64_t pairwise_scratch_size(uint64_t count);
 // *out = sum of `count` unsigned values (zeroed first, on stream s).
 hipError_t launch_sum_visited(const unsigned* in, uint64_t count, unsigned long long* out, hipStream_t s);
+// walk_sparse counts the chunks it ended (walk_sparse.hip count_chunk_end) in
+// kChunkEndWords unsigned words, zero before the launch; their sum is the
+// count.  The wave holding ticket g adds to word chunk_end_word(g): one word in
+// 64 bytes, so the adds of waves with neighbouring tickets meet in no line.
+constexpr unsigned kChunkEndSlots = 1024, kChunkEndWords = kChunkEndSlots * 16;
+constexpr unsigned chunk_end_word(unsigned g) { return (g & (kChunkEndSlots - 1u)) * 16u; }
 // The same tree over each of `nseg` consecutive segments of `count` doubles
 // (a leaf batch's chunk partials): out[i] is bit-identical to
 // launch_pairwise_reduce over segment i alone.  `scratch` holds nseg times

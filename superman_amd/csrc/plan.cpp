@@ -629,7 +629,7 @@ static uint64_t seg_disk_key(const double* A, int n, const Layout& lay) {
   Fnv1a f{0x5eed5e9a11ull ^ jit_toolchain_hash()};
   const size_t nn = (size_t)n * n;
   const bool integral = is_integral(A, n);
-  const int32_t head[] = {6 /* format: bump when the planner changes */, n, lay.L, lay.m, (int32_t)lay.fixed, (int32_t)integral};
+  const int32_t head[] = {7 /* format: bump when the planner changes */, n, lay.L, lay.m, (int32_t)lay.fixed, (int32_t)integral};
   f.bytes(head, sizeof head);
   if (integral) {
     f.bytes(A, nn * sizeof(double));

@@ -32,6 +32,22 @@
 
 namespace sup {
 
+// An ended chunk is counted where it ends, so that the host can report the
+// states that were walked (run_range: RangeResult::visited): one add without a
+// return value to the word of its ticket (kernels.hpp chunk_end_word) in
+// WalkParams::visited — those words lie behind the per-chunk words that
+// chunk_store's unfused path writes (zeros here), or at the front when the
+// walk folds its partials.  Every operand is read here, on the ended chunk's
+// path, or is live for chunk_store anyway: nothing more is held across the
+// walk loop, whose registers are the kernel's.
+__device__ __forceinline__ void count_chunk_end(uint32_t lane, uint32_t g) {
+  unsigned int* vis = SUP_KARG(visited);
+  if (vis && lane == 0) {
+    const uint64_t first = SUP_KARG(fold_cnt) ? 0ull : SUP_KARG(chunk_count);
+    (void)__hip_atomic_fetch_add(vis + first + chunk_end_word(g), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 template <int N>
 __global__ __launch_bounds__(kBlock) void walk_sparse(WalkParams p) {
   constexpr int NP = pad8(N);
@@ -53,6 +69,7 @@ __global__ __launch_bounds__(kBlock) void walk_sparse(WalkParams p) {
       chunk_start<N>(x, p, ga, lane);
       if (zero_rows<N>(x) & SUP_KARG(umask)) {  // chunk end: every term an exact zero
         keep = (lane == j) ? 0.0 : keep;
+        count_chunk_end(lane, g);
         continue;
       }
       double U[NB + 1];

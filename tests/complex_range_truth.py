@@ -1,7 +1,9 @@
 """Exact truth for the range entry of the complex double-double walk
 (sup_perman_complex_quad_range) over Gaussian integers and
-fractions.Fraction: shared by test_complex_quad.py and test_gpu_complex_quad.py.
-Nothing here calls the engine or the oracle.
+fractions.Fraction: shared by test_complex_quad.py and test_gpu_complex_quad.py,
+and (range_sum_abs: the sum and the scale of its tolerance) by the per-order
+tests of the complex fp64 walk, test_fp64_range.py and
+test_gpu_complex_orders.py.  Nothing here calls the engine or the oracle.
 
 It is range_truth.range_sum's enumeration with complex values and the identity
 column map: a range of wave-chunks [c0, c1) of a plan with L lane bits and m
@@ -73,6 +75,70 @@ def range_sum_float(a, L, m, c0, c1):
     assert all(Fraction(ints[j][c][p], 2 << s) == fr[j][c][p] for j in range(n) for c in range(n) for p in (0, 1))
     tr, ti = range_sum(ints, L, m, c0, c1)
     return Fraction(tr, 1 << (n * (s + 1))), Fraction(ti, 1 << (n * (s + 1)))
+
+
+def range_sum_abs(A, L, m, c0, c1):
+    """range_sum with a second accumulator: (re, im, scale) with scale the exact
+    sum of |Re term| + |Im term| over the same subsets (the fp64 walk's
+    tolerance is a multiple of it: test_fp64_range.py).  A step touches the
+    nonzeros of its column only."""
+    n = len(A)
+    lo = L + m
+    assert lo <= n - 1
+    sums = [(sum(z[0] for z in row), sum(z[1] for z in row)) for row in A]
+    assert all(s[0] % 2 == 0 and s[1] % 2 == 0 for s in sums)
+    xr = [A[j][n - 1][0] - sums[j][0] // 2 for j in range(n)]
+    xi = [A[j][n - 1][1] - sums[j][1] // 2 for j in range(n)]
+    cols = [[(j, A[j][e][0], A[j][e][1]) for j in range(n) if A[j][e] != (0, 0)] for e in range(n - 1)]
+
+    def cprod(r, i):
+        pr, pi = 1, 0
+        for u, v in zip(r, i):
+            pr, pi = pr * u - pi * v, pr * v + pi * u
+        return pr, pi
+
+    tr = ti = scale = 0
+    for a in range(c0, c1):
+        r, i = list(xr), list(xi)
+        sign = 1
+        g, e = a ^ (a >> 1), lo
+        while g:
+            if g & 1:
+                for j, u, v in cols[e]:
+                    r[j] += u
+                    i[j] += v
+                sign = -sign
+            g >>= 1
+            e += 1
+        pr, pi = cprod(r, i)
+        tr, ti, scale = tr + sign * pr, ti + sign * pi, scale + abs(pr) + abs(pi)
+        for t in range(1, 1 << lo):
+            k = (t & -t).bit_length() - 1
+            if ((t >> k) ^ (t >> (k + 1))) & 1:  # bit k of gray(t): set by this step
+                for j, u, v in cols[k]:
+                    r[j] += u
+                    i[j] += v
+            else:
+                for j, u, v in cols[k]:
+                    r[j] -= u
+                    i[j] -= v
+            sign = -sign
+            pr, pi = cprod(r, i)
+            tr, ti, scale = tr + sign * pr, ti + sign * pi, scale + abs(pr) + abs(pi)
+    return tr, ti, scale
+
+
+def range_sum_abs_float(a, L, m, c0, c1):
+    """(re, im, scale) for a complex128 matrix, as Fractions: range_sum_float's
+    scaling of range_sum_abs."""
+    n = len(a)
+    fr = [[(Fraction(float(complex(z).real)), Fraction(float(complex(z).imag))) for z in row] for row in a]
+    s = max(p.denominator for row in fr for z in row for p in z).bit_length() - 1
+    ints = [[(int(2 * z[0] * (1 << s)), int(2 * z[1] * (1 << s))) for z in row] for row in fr]
+    assert all(Fraction(ints[j][c][p], 2 << s) == fr[j][c][p] for j in range(n) for c in range(n) for p in (0, 1))
+    den = 1 << (n * (s + 1))
+    tr, ti, scale = range_sum_abs(ints, L, m, c0, c1)
+    return Fraction(tr, den), Fraction(ti, den), Fraction(scale, den)
 
 
 def subsets(L, m, c0, c1):

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SUP_ABI_VERSION 20  /* 20: sup_hafnian_complex, sup_loop_hafnian_complex, sup_hafnian_complex_plan; 19: sup_perman_complex_exact, sup_perman_complex_exact_range, SUP_CPLX_EXACT_MAX_DEVICE_N; 18: sup_perman_complex_quad, sup_perman_complex_quad_range, SUP_CPLX_QUAD_MAX_DEVICE_N; 17:sup_perman_complex_fock_minors, sup_perman_complex_fock_minors_plan, sup_boson_sample_fock; 16: sup_plan_census; 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
+#define SUP_ABI_VERSION 21  /* 21: sup_hafnian_complex_pt, sup_loop_hafnian_complex_pt, sup_hafnian_complex_pt_range, sup_hafnian_complex_pt_plan, SUP_HAFNIAN_PT_MAX_DEVICE_N; 20: sup_hafnian_complex, sup_loop_hafnian_complex, sup_hafnian_complex_plan; 19: sup_perman_complex_exact, sup_perman_complex_exact_range, SUP_CPLX_EXACT_MAX_DEVICE_N; 18: sup_perman_complex_quad, sup_perman_complex_quad_range, SUP_CPLX_QUAD_MAX_DEVICE_N; 17:sup_perman_complex_fock_minors, sup_perman_complex_fock_minors_plan, sup_boson_sample_fock; 16: sup_plan_census; 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SUP_OK            0
@@ -727,6 +727,61 @@ int sup_loop_hafnian_complex(const double* A, int M, const double* mu, const int
 /* The terms T of each matrix's sum, host only (no device).  terms may be NULL.
  * A null list or n outside [1, 64]: SUP_EINVAL.  Indices are only compared. */
 int sup_hafnian_complex_plan(const int32_t* idx, int n, uint64_t count, uint64_t* terms);
+
+/* Power-trace hafnians and loop hafnians (ABI 21): the same gathers and the
+ * same mathematical values as sup_hafnian_complex / sup_loop_hafnian_complex by
+ * a second, independent algorithm (Bjorklund, Gupt, Quesada) whose cost does
+ * not depend on repeats: with n' = n + (n odd, loop form: one virtual index
+ * with a zero row and column and mu = 1), m = n' / 2, the sum runs over the
+ * non-empty subsets z of the m index pairs (2i, 2i + 1),
+ *   haf = sum_{z in [1, 2^m)} (-1)^(m - |z|) f(z),   f(z) = g_m,
+ *   g_0 = 1,  g_s = (1 / s) sum_{j=1..s} (j c_j) g_(s-j),
+ *   c_j = tr (N_z X)^j / (2j) + (d_z X (N_z X)^(j-1) d_z) / 2
+ * (N_z: the rows and columns of the pairs of z, X: the pair swap, d = mu on
+ * the list, the second term in the loop form only); 2^(n/2) subsets of
+ * n^3-sized work instead of 2^(n-1) states (the order of every
+ * operation is superman_amd/csrc/hafpt.hpp's).  Odd n in the plain form gives
+ * exactly 0 and visits nothing.  out[2k], out[2k + 1] = Re, Im of result k: a
+ * function of (A, mu, idx[k]) only, bit-identical on the device
+ * (walk_hafpt.hip), on any device count (o->gpu_num devices take contiguous
+ * ranges of matrices), for any queue group and on host threads (on_cpu = 1).
+ * It is NOT bit-identical to sup_hafnian_complex: the two check each other to
+ * rounding.
+ * Errors, all before any device work: a null pointer, n outside [1, 64], an
+ * index outside [0, M), a pair A[i][j], A[j][i] that differs: SUP_EINVAL with a
+ * message naming the place; on_cpu = 0 and n above
+ * SUP_HAFNIAN_PT_MAX_DEVICE_N: SUP_EUNSUPPORTED (on any machine; host threads
+ * serve every n <= 64); no device with on_cpu = 0: SUP_ENODEV (no CPU
+ * fallback).  The cap is the largest order whose kernel uses no scratch memory
+ * and whose LDS tile (n'^2 + 163 complex values) fits one 64 KiB workgroup
+ * allocation, two of which share a compute unit.
+ * st: leaves = count, gray_steps = count 2^(n-1) (nominal, as the Kan
+ * entries'), visited_steps = the subsets visited, kernel_ms, wall_ms,
+ * devices_used, grid, est_ops_per_step = fp64 operations per subset (the
+ * census hafpt_ops(m, loop) of DESIGN.md 8i, binomial mean over |z|). */
+#define SUP_HAFNIAN_PT_MAX_DEVICE_N 62
+int sup_hafnian_complex_pt(const double* A, int M, const int32_t* idx, int n, uint64_t count, const sup_opts* o,
+                           int on_cpu, double* out, sup_stats* st);
+int sup_loop_hafnian_complex_pt(const double* A, int M, const double* mu, const int32_t* idx, int n, uint64_t count,
+                                const sup_opts* o, int on_cpu, double* out, sup_stats* st);
+/* One matrix (one list of n indices), the subsets z in [max(1, z_begin), z_end)
+ * only; mu non-null: the loop form.  A wave-chunk is 2^max(0, m - 18)
+ * consecutive z; its partial is the ascending-z sum of the signed f(z) of the
+ * range that fall in it, and out[0], out[1] = the fold of the partials of the
+ * chunks the range touches, by the pairwise tree over (chunk - first chunk).
+ * Ranges cut where such trees meet (aligned power-of-two runs of chunks)
+ * added pairwise in order reproduce the whole range's bits, and the whole
+ * range [0, 2^m) has the batch entries' bits.  z_begin > z_end or z_end > 2^m:
+ * SUP_EINVAL; an empty range, or odd n in the plain form: zeros.  One device
+ * (o->device_id) or host threads; the other errors as above.
+ * st: visited_steps = the subsets of the range, gray_steps = 2^(n-1). */
+int sup_hafnian_complex_pt_range(const double* A, int M, const double* mu_or_null, const int32_t* idx, int n,
+                                 uint64_t z_begin, uint64_t z_end, const sup_opts* o, int on_cpu, double* out,
+                                 sup_stats* st);
+/* The subsets one matrix of order n visits (2^m - 1; 0 for odd n in the plain
+ * form) and the census' fp64 operations per subset.  Host only; either output
+ * may be NULL.  n outside [1, 64]: SUP_EINVAL. */
+int sup_hafnian_complex_pt_plan(int n, int loop, uint64_t* subsets, double* est_ops);
 
 /* Nijenhuis-Wilf prologue (gpu_exact_dense.cu:642-652): x0[j] = a[j][n-1] - rowsum_j/2,
  * p0 = prod x0.  Host-only helper, exported for the test harness. */

@@ -22,6 +22,8 @@ from ._lib import (KERNEL_DENSE, KERNEL_SKIPPER, KERNEL_SPARYSER, LEAF_FN, SCHED
 __all__ = [
     "perman", "perman_cpu", "perman_exact", "perman_exact_range", "perman_quad", "perman_quad_range", "perman_complex", "perman_complex_range", "perman_complex_quad", "perman_complex_quad_range", "COMPLEX_QUAD_MAX_DEVICE_N", "perman_complex_exact", "perman_complex_exact_range", "COMPLEX_EXACT_MAX_DEVICE_N", "perman_complex_batch", "perman_complex_submatrices", "perman_complex_fock", "perman_complex_fock_plan", "perman_complex_fock_minors", "perman_complex_fock_minors_submatrices",
            "hafnian", "loop_hafnian", "hafnian_repeated", "hafnian_batch", "hafnian_plan",
+           "hafnian_powertrace", "loop_hafnian_powertrace", "hafnian_powertrace_batch", "hafnian_powertrace_range",
+           "hafnian_powertrace_plan", "HAFNIAN_PT_MAX_DEVICE_N",
            "perman_complex_fock_minors_plan","perman_complex_minors", "perman_complex_minors_submatrices", "perman_complex_minors_range", "boson_sample", "read_mtx_complex", "partial", "perman_shard", "plan_info", "plan_census", "CENSUS_CLASSES", "plan_key", "prepare", "read_matrix", "read_mtx", "sort_order",
     "skip_order", "compress", "decompose", "perman_reduced", "approx", "grid_graph", "ALGOS_APPROX",
     "nw_start", "device_count", "rccl_devices", "layout", "ShardCall", "SupError", "ALGOS_DENSE", "ALGOS_SPARSE",
@@ -800,6 +802,94 @@ def hafnian_plan(idx):
     terms = np.zeros(max(count, 1), np.uint64)
     _lib.check(_lib.load().sup_hafnian_complex_plan(i32.ctypes.data, n, count, terms.ctypes.data), "hafnian_plan")
     return int(terms[0]) if single else terms[:count].copy()
+
+
+# include/superman.h SUP_HAFNIAN_PT_MAX_DEVICE_N: the largest order the
+# power-trace kernel serves on the device (host threads serve n <= 64)
+HAFNIAN_PT_MAX_DEVICE_N = 62
+
+
+def _haf_matrix(A, mu, loop):
+    a = np.ascontiguousarray(np.asarray(A, dtype=np.complex128))
+    if a.ndim != 2 or a.shape[0] != a.shape[1] or a.shape[0] < 1:
+        raise ValueError(f"expected a non-empty square matrix A, got shape {a.shape}")
+    m = None
+    if loop:
+        m = np.ascontiguousarray(np.diag(a) if mu is None else np.asarray(mu, dtype=np.complex128))
+        if m.shape != (a.shape[0],):
+            raise ValueError(f"mu must have shape [{a.shape[0]}], got {m.shape}")
+    return a, m
+
+
+def hafnian_powertrace_batch(A, idx, mu=None, loop: bool = False, gpu_num: int = 1, device_id: int = 0,
+                             cpu: bool = False, threads: int = 16, return_stats: bool = False):
+    """The hafnians (``loop=True``: the loop hafnians) of the gathers
+    ``A[np.ix_(idx[k], idx[k])]`` by the power-trace algorithm
+    (sup_hafnian_complex_pt, sup_loop_hafnian_complex_pt): 2^(n/2) subsets of
+    n^3-sized work each instead of ``hafnian_batch``'s 2^(n-1) states, whatever
+    the repeats (the kernel walk_hafpt.hip, or (cpu=True) its host twin,
+    bit-identical).  Arguments and shapes as ``hafnian_batch``; the values agree
+    with it to rounding, not bit for bit.  On the device n <=
+    ``HAFNIAN_PT_MAX_DEVICE_N``; host threads serve n <= 64."""
+    a, m = _haf_matrix(A, mu, loop)
+    i32, count, n, single = _haf_lists(idx)
+    lib = _lib.load()
+    o = _opts(gpu_num=gpu_num, device_id=device_id, threads=threads)
+    out, st = np.zeros(2 * max(count, 1)), SupStats()
+    if loop:
+        rc = lib.sup_loop_hafnian_complex_pt(a.ctypes.data, a.shape[0], m.ctypes.data, i32.ctypes.data, n, count,
+                                             C.byref(o), int(bool(cpu)), out.ctypes.data, C.byref(st))
+    else:
+        rc = lib.sup_hafnian_complex_pt(a.ctypes.data, a.shape[0], i32.ctypes.data, n, count, C.byref(o),
+                                        int(bool(cpu)), out.ctypes.data, C.byref(st))
+    _lib.check(rc, "loop_hafnian_powertrace" if loop else "hafnian_powertrace")
+    v = _batch_result(out, count)
+    v = complex(v[0]) if single else v
+    return (v, st.as_dict()) if return_stats else v
+
+
+def hafnian_powertrace(A, **kw):
+    """The hafnian of the whole complex symmetric matrix A by the power-trace
+    algorithm (``hafnian_powertrace_batch`` with idx = 0..n-1)."""
+    return hafnian_powertrace_batch(A, np.arange(np.shape(A)[0]), **kw)
+
+
+def loop_hafnian_powertrace(A, mu=None, **kw):
+    """The loop hafnian of the whole matrix A by the power-trace algorithm;
+    ``mu`` defaults to its diagonal."""
+    return hafnian_powertrace_batch(A, np.arange(np.shape(A)[0]), mu=mu, loop=True, **kw)
+
+
+def hafnian_powertrace_range(A, idx, z_begin: int, z_end: int, mu=None, loop: bool = False, device_id: int = 0,
+                             cpu: bool = False, threads: int = 16, return_stats: bool = False):
+    """The part of one list's power-trace sum from the subsets z in
+    [max(1, z_begin), z_end) (sup_hafnian_complex_pt_range): the chunk
+    partials of the range folded pairwise.  The whole range [0, 2^m) has
+    ``hafnian_powertrace_batch``'s bits."""
+    a, m = _haf_matrix(A, mu, loop)
+    i32, count, n, single = _haf_lists(idx)
+    if not single:
+        raise ValueError("hafnian_powertrace_range takes one index list of shape [n]")
+    if not (0 <= int(z_begin) < 2**64 and 0 <= int(z_end) < 2**64):
+        raise ValueError("z_begin and z_end must be unsigned 64-bit integers")
+    lib = _lib.load()
+    o = _opts(gpu_num=1, device_id=device_id, threads=threads)
+    out, st = np.zeros(2), SupStats()
+    rc = lib.sup_hafnian_complex_pt_range(a.ctypes.data, a.shape[0], m.ctypes.data if loop else None, i32.ctypes.data,
+                                          n, int(z_begin), int(z_end), C.byref(o), int(bool(cpu)), out.ctypes.data,
+                                          C.byref(st))
+    _lib.check(rc, "hafnian_powertrace_range")
+    v = complex(out[0], out[1])
+    return (v, st.as_dict()) if return_stats else v
+
+
+def hafnian_powertrace_plan(n: int, loop: bool = False):
+    """(subsets, fp64 operations per subset) of one matrix of order n
+    (sup_hafnian_complex_pt_plan, host only)."""
+    subsets, ops = C.c_uint64(0), C.c_double(0.0)
+    _lib.check(_lib.load().sup_hafnian_complex_pt_plan(int(n), int(bool(loop)), C.byref(subsets), C.byref(ops)),
+               "hafnian_powertrace_plan")
+    return int(subsets.value), float(ops.value)
 
 
 def partial(mat, start: int, end: int, kernel: str = "dense", gpu_num: int = 1, device_id: int = 0,

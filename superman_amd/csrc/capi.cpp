@@ -7,6 +7,7 @@
 
 #include "dd.hpp"
 #include "engine.hpp"
+#include "hafnian_pt.hpp"
 
 using namespace sup;
 
@@ -652,6 +653,56 @@ int sup_loop_hafnian_complex(const double* A, int M, const double* mu, const int
 
 int sup_hafnian_complex_plan(const int32_t* idx, int n, uint64_t count, uint64_t* terms) {
   return hafnian_plan(idx, n, count, terms);
+}
+
+static int hafnian_pt_entry(const HafIn& in, int n, uint64_t count, bool range, uint64_t z0, uint64_t z1,
+                            const sup_opts* o_in, int on_cpu, double* out, sup_stats* st) {
+  auto t0 = std::chrono::steady_clock::now();
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  if (range) o.gpu_num = 1;
+  PtInfo pi;
+  if (int rc = hafnian_pt(in, n, count, range, z0, z1, o, on_cpu != 0, out, &pi)) return rc;
+  if (st) {
+    std::memset(st, 0, sizeof(*st));
+    st->kernel_ms = pi.kernel_ms;
+    st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    st->gray_steps = count << (n - 1);  // nominal: the Kan walk without repeats
+    st->visited_steps = pi.subsets;
+    st->devices_used = pi.devices;
+    st->grid = pi.grid;
+    st->walk_kind = (int)kWalkDense;
+    st->leaves = (int)std::min<uint64_t>(count, 0x7fffffffu);
+    st->est_ops_per_step = pi.ops;
+  }
+  return SUP_OK;
+}
+
+int sup_hafnian_complex_pt(const double* A, int M, const int32_t* idx, int n, uint64_t count, const sup_opts* o,
+                           int on_cpu, double* out, sup_stats* st) {
+  HafIn in;
+  in.A = A, in.M = M, in.idx = idx;
+  return hafnian_pt_entry(in, n, count, false, 0, 0, o, on_cpu, out, st);
+}
+
+int sup_loop_hafnian_complex_pt(const double* A, int M, const double* mu, const int32_t* idx, int n, uint64_t count,
+                                const sup_opts* o, int on_cpu, double* out, sup_stats* st) {
+  HafIn in;
+  in.A = A, in.M = M, in.mu = mu, in.idx = idx, in.loop = true;
+  return hafnian_pt_entry(in, n, count, false, 0, 0, o, on_cpu, out, st);
+}
+
+int sup_hafnian_complex_pt_range(const double* A, int M, const double* mu_or_null, const int32_t* idx, int n,
+                                 uint64_t z_begin, uint64_t z_end, const sup_opts* o, int on_cpu, double* out,
+                                 sup_stats* st) {
+  HafIn in;
+  in.A = A, in.M = M, in.mu = mu_or_null, in.idx = idx, in.loop = mu_or_null != nullptr;
+  return hafnian_pt_entry(in, n, 1, true, z_begin, z_end, o, on_cpu, out, st);
+}
+
+int sup_hafnian_complex_pt_plan(int n, int loop, uint64_t* subsets, double* est_ops) {
+  return hafnian_pt_plan(n, loop, subsets, est_ops);
 }
 
 // sup_stats of a minors call: the batch entry's, with the one-walk step cost.

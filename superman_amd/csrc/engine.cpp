@@ -3,6 +3,7 @@
 // (run_range, run_range_batch, run_range_exact, run_range_dd, warm_devices).
 // Plans come from plan.cpp; the schedulers that call these are schedule.cpp.
 #include "engine.hpp"
+#include "hafnian_pt.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -1481,6 +1482,82 @@ int run_hafnian(int dev, const HafSlab& S, const HafIn& in, double* out, double*
                              reinterpret_cast<const int32_t*>(c->d_fock + u_grp), p.mats, K, c->d_cbtab, s));
   SUP_HIP(launch_haf(S.loop, p, (int)geo.grid, s));
   SUP_HIP(launch_haf_fold(c->d_chunk, p.mats, K, S.div, c->d_cbout, s));
+  SUP_HIP(hipEventRecord(c->ev1, s));
+  SUP_HIP(hipMemcpyAsync(out, c->d_cbout, (size_t)(K * 2) * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (grid_out) *grid_out = (int)geo.grid;
+  return timed_sync(c, kernel_ms);
+}
+
+// Power-trace hafnian kernel (walk_hafpt.hip) on matrices [first, first + K) of
+// in.idx, subsets [z_begin, z_end) of each: A, mu, the index lists and the
+// coefficient table go up, then prepare (tables gathered on the device), the
+// walk over the slab's queue and the per-matrix fold run on the context's
+// stream, and one download brings 16 bytes per matrix into out.  The buffers
+// are the collision-aware walk's (same context lock).
+int run_hafnian_pt(int dev, const HafIn& in, int n, int np, uint64_t first, uint64_t K, uint64_t z_begin,
+                   uint64_t z_end, const double* coef, double* out, double* kernel_ms, int* grid_out) {
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (grid_out) *grid_out = 0;
+  if (K == 0) return SUP_OK;
+  const int m = np / 2, llog = hafpt_chunk_log(m);
+  if (n < 1 || np != n + (n & 1) || np > SUP_HAFNIAN_PT_MAX_DEVICE_N || hafpt_lds_bytes(np) > 65536 || !out || !in.A ||
+      !in.idx || in.M < 1 || (in.loop && !in.mu) || !coef || z_begin >= z_end || z_end > (1ull << m)) {
+    set_error("run_hafnian_pt: bad request");
+    return SUP_EINVAL;
+  }
+  const uint64_t cfirst = z_begin >> llog, cm = ((z_end + (1ull << llog) - 1) >> llog) - cfirst;
+  const uint64_t chunks = K * cm, tab_doubles = 2 * hafpt_pairs(np);
+  if (cm > 0xffffffffull || chunks > 0x7fffffffull) {
+    set_error("run_hafnian_pt: too many wave-chunks in one slab");
+    return SUP_EINVAL;
+  }
+  const size_t a_doubles = (size_t)2 * in.M * in.M, mu_doubles = in.loop ? (size_t)2 * in.M : 0;
+  const size_t u_coef = (kPtCoef * sizeof(double) + 15) / 16;
+  CtxGuard guard;
+  int rc = guard.open(dev, "device buffers");
+  if (rc) return rc;
+  DeviceCtx* c = guard.c;
+  int occ = 0;
+  SUP_HIP(hafpt_occupancy(in.loop, np, &occ));
+  if ((rc = ensure(c->d_cbtab, c->cbtab_cap, (size_t)(K * tab_doubles)))) return rc;
+  if ((rc = ensure(c->d_cbidx, c->cbidx_cap, (size_t)K * n))) return rc;
+  if ((rc = ensure(c->d_cbU, c->cbU_cap, a_doubles + mu_doubles))) return rc;
+  if ((rc = ensure(c->d_chunk, c->chunk_cap, (size_t)(2 * chunks)))) return rc;
+  if ((rc = ensure(c->d_cbout, c->cbout_cap, (size_t)(K * 2)))) return rc;
+  if ((rc = ensure(c->d_fock, c->fock_cap, u_coef))) return rc;
+  hipStream_t s = c->stream;
+  c->tables_uid = 0;  // the walk leaves head 0 nonzero
+  c->head_zero[0] = false;
+  SUP_HIP(hipMemcpyAsync(c->d_cbU, in.A, a_doubles * sizeof(double), hipMemcpyHostToDevice, s));
+  if (mu_doubles)
+    SUP_HIP(hipMemcpyAsync(c->d_cbU + a_doubles, in.mu, mu_doubles * sizeof(double), hipMemcpyHostToDevice, s));
+  SUP_HIP(hipMemcpyAsync(c->d_cbidx, in.idx + first * n, (size_t)K * n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  SUP_HIP(hipMemcpyAsync(c->d_fock, coef, kPtCoef * sizeof(double), hipMemcpyHostToDevice, s));
+  SUP_HIP(hipMemsetAsync(c->d_counter, 0, sizeof(unsigned), s));
+  const uint64_t resident = (uint64_t)c->cus * (uint64_t)std::max(occ, 1);
+  const char* fg = std::getenv("SUP_WALK_GROUP");  // tests, read per call: chunks per ticket (the bits do not change)
+  const LaunchGeom geo = walk_geometry(chunks, resident, 1, false, fg ? std::max(1, std::atoi(fg)) : 0);
+  PtParams p{};
+  p.tabs = c->d_cbtab;
+  p.coef = reinterpret_cast<const double*>(c->d_fock);
+  p.chunk_count = chunks;
+  p.chunk_out = c->d_chunk;
+  p.counter = c->d_counter;
+  p.group = geo.group;
+  p.np = (unsigned)np;
+  p.m = (unsigned)m;
+  p.llog = (unsigned)llog;
+  p.cm = (unsigned)cm;
+  p.tab_doubles = (unsigned)tab_doubles;
+  p.z_begin = z_begin;
+  p.z_end = z_end;
+  p.chunk_first = cfirst;
+  SUP_HIP(hipEventRecord(c->ev0, s));
+  SUP_ON_DEVICE(c->dev, "power-trace hafnian launch");
+  SUP_HIP(launch_hafpt_prepare(c->d_cbU, in.M, in.loop ? c->d_cbU + a_doubles : nullptr, c->d_cbidx, n, np, K,
+                               (uint32_t)tab_doubles, c->d_cbtab, s));
+  SUP_HIP(launch_hafpt(in.loop, p, (int)geo.grid, s));
+  SUP_HIP(launch_hafpt_fold(c->d_chunk, (uint32_t)cm, K, c->d_cbout, s));
   SUP_HIP(hipEventRecord(c->ev1, s));
   SUP_HIP(hipMemcpyAsync(out, c->d_cbout, (size_t)(K * 2) * sizeof(double), hipMemcpyDeviceToHost, s));
   if (grid_out) *grid_out = (int)geo.grid;

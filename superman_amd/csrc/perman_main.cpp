@@ -42,6 +42,9 @@
 // takes mode k rpt[k] times (default: every mode once).  -g the device walk,
 // -c the host threads; prints "Hafnian: <re> <im>".  Refused with the options
 // --complex is refused with and with the --complex flags.
+// --hafnian --powertrace: the same value through sup_hafnian_complex_pt /
+// sup_loop_hafnian_complex_pt (2^(n/2) subsets instead of 2^(n-1) states; on
+// the device up to n = SUP_HAFNIAN_PT_MAX_DEVICE_N, with -c up to 64).
 #include <getopt.h>
 
 #include <chrono>
@@ -61,7 +64,7 @@ struct Cli {
   bool generic = true, dense = true, approximation = false, gpu = false, cpu = false, grid_graph = false;
   bool rccl = false, verbose = false, compression = false, exact = false, quad = false;
   bool half_calc = false, half_store = false, complex = false, complex_quad = false, complex_exact = false, preprocessing_given = false, gpu_num_given = false;
-  bool hafnian = false, loop = false;
+  bool hafnian = false, loop = false, powertrace = false;
   int gpu_num = 2, threads = 16, perman_algo = 1, preprocessing = 0, device = 0, reps = 1;
   double scaling = -1.0;
   long number_of_times = 100000;  // main.cu:338-344 defaults
@@ -261,12 +264,17 @@ int run_hafnian_cli(const Cli& c) {
   int rc = SUP_OK;
   const auto t0 = std::chrono::steady_clock::now();
   for (int rep = 0; rep < c.reps && rc == SUP_OK; ++rep)
-    rc = c.loop ? sup_loop_hafnian_complex(mat, M, mu.data(), idx.data(), (int)idx.size(), 1, &o, c.gpu ? 0 : 1, out, &st)
-                : sup_hafnian_complex(mat, M, idx.data(), (int)idx.size(), 1, &o, c.gpu ? 0 : 1, out, &st);
+    if (c.powertrace)
+      rc = c.loop ? sup_loop_hafnian_complex_pt(mat, M, mu.data(), idx.data(), (int)idx.size(), 1, &o, c.gpu ? 0 : 1, out, &st)
+                  : sup_hafnian_complex_pt(mat, M, idx.data(), (int)idx.size(), 1, &o, c.gpu ? 0 : 1, out, &st);
+    else
+      rc = c.loop ? sup_loop_hafnian_complex(mat, M, mu.data(), idx.data(), (int)idx.size(), 1, &o, c.gpu ? 0 : 1, out, &st)
+                  : sup_hafnian_complex(mat, M, idx.data(), (int)idx.size(), 1, &o, c.gpu ? 0 : 1, out, &st);
   const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / (double)c.reps;
   sup_free(mat);
   if (rc != SUP_OK) return fail(c.loop ? "loop hafnian" : "hafnian");
-  std::cout << "Result: " << (c.gpu ? "gpu_" : "cpu_") << (c.loop ? "loop_hafnian64_complex" : "hafnian64_complex") << " "
+  std::cout << "Result: " << (c.gpu ? "gpu_" : "cpu_") << (c.loop ? "loop_hafnian64_complex" : "hafnian64_complex")
+            << (c.powertrace ? "_powertrace" : "") << " "
             << out[0] << " " << out[1] << " in " << sec << std::endl;
   std::printf("Hafnian: %.17e %.17e\n", out[0], out[1]);
   if (c.verbose)
@@ -301,6 +309,7 @@ int main(int argc, char** argv) {
                                         {"hafnian", 0, NULL, 1003},
                                         {"loop", 0, NULL, 1004},
                                         {"rpt", 1, NULL, 1005},
+                                        {"powertrace", 0, NULL, 1006},
                                         {NULL, 0, NULL, 0}};
   int opt;
   auto need_arg = [&](char o) -> bool {
@@ -342,6 +351,7 @@ int main(int argc, char** argv) {
       case 1003: c.hafnian = true; break;
       case 1004: c.loop = true; break;
       case 1005: c.rpt = optarg; break;
+      case 1006: c.powertrace = true; break;
       case 'v': c.verbose = true; break;
       // v2 flags (revised_perman/main.cpp:1431-1460): -w stores the matrix in
       // single precision (the permanent of the float-rounded entries); -h asks
@@ -370,6 +380,10 @@ int main(int argc, char** argv) {
   for (int i = optind; i < argc; ++i) std::printf("Non-option argument %s\n", argv[i]);
   if (!c.cpu && !c.gpu) c.gpu = true;  // main.cu:482-484
   if (c.hafnian) return run_hafnian_cli(c);
+  if (c.powertrace) {
+    std::fprintf(stderr, "perman: --powertrace goes with --hafnian\n");
+    return 1;
+  }
   if (c.loop || !c.rpt.empty()) {
     std::fprintf(stderr, "perman: --loop and --rpt go with --hafnian\n");
     return 1;

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SUP_ABI_VERSION 21  /* 21: sup_hafnian_complex_pt, sup_loop_hafnian_complex_pt, sup_hafnian_complex_pt_range, sup_hafnian_complex_pt_plan, SUP_HAFNIAN_PT_MAX_DEVICE_N; 20: sup_hafnian_complex, sup_loop_hafnian_complex, sup_hafnian_complex_plan; 19: sup_perman_complex_exact, sup_perman_complex_exact_range, SUP_CPLX_EXACT_MAX_DEVICE_N; 18: sup_perman_complex_quad, sup_perman_complex_quad_range, SUP_CPLX_QUAD_MAX_DEVICE_N; 17:sup_perman_complex_fock_minors, sup_perman_complex_fock_minors_plan, sup_boson_sample_fock; 16: sup_plan_census; 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
+#define SUP_ABI_VERSION 22  /* 22: sup_torontonian, sup_torontonian_range, sup_torontonian_plan, SUP_TORONTONIAN_MAX_DEVICE_N; 21: sup_hafnian_complex_pt, sup_loop_hafnian_complex_pt, sup_hafnian_complex_pt_range, sup_hafnian_complex_pt_plan, SUP_HAFNIAN_PT_MAX_DEVICE_N; 20: sup_hafnian_complex, sup_loop_hafnian_complex, sup_hafnian_complex_plan; 19: sup_perman_complex_exact, sup_perman_complex_exact_range, SUP_CPLX_EXACT_MAX_DEVICE_N; 18: sup_perman_complex_quad, sup_perman_complex_quad_range, SUP_CPLX_QUAD_MAX_DEVICE_N; 17:sup_perman_complex_fock_minors, sup_perman_complex_fock_minors_plan, sup_boson_sample_fock; 16: sup_plan_census; 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SUP_OK            0
@@ -782,6 +782,52 @@ int sup_hafnian_complex_pt_range(const double* A, int M, const double* mu_or_nul
  * form) and the census' fp64 operations per subset.  Host only; either output
  * may be NULL.  n outside [1, 64]: SUP_EINVAL. */
 int sup_hafnian_complex_pt_plan(int n, int loop, uint64_t* subsets, double* est_ops);
+
+/* Torontonians (ABI 22): the probabilities of click patterns of Gaussian boson
+ * sampling with threshold detectors.  O is 2M x 2M complex Hermitian, row-major
+ * pairs, in thewalrus' ordering (row i: mode i, row i + M: its conjugate
+ * partner).  Only its lower triangle and the real parts of its diagonal are
+ * read, as LAPACK does: a matrix that is Hermitian only to rounding is not
+ * refused.  A list of n DISTINCT modes s selects the 2n rows and columns {s_b,
+ * s_b + M}; bit b of z in [0, 2^n) selects list position b:
+ *   tor(O, s) = sum_z (-1)^(n - |z|) f(z),  f(z) = 1 / sqrt det(I - O_z),  f(0) = 1
+ * with O_z the principal submatrix of the selected positions; f(z) is the
+ * product of the reciprocal pivots of a Cholesky factorisation whose row order
+ * and operation order superman_amd/csrc/tor.hpp fixes, so that
+ * subsets sharing their high bits share the leading rows of the factor.
+ * modes: count lists of n (int32); out: count doubles (the result is real).
+ * out[k] is a function of (O, modes[k]) only, bit-identical on the device
+ * (walk_tor.hip), on any device count (o->gpu_num devices take contiguous
+ * ranges of lists), for any queue group and on host threads (on_cpu = 1).
+ * A pivot that is not positive (I - O_z not positive definite) is no error
+ * code: that list's result is NaN.
+ * Errors, all before any device work: a null pointer, n outside [1, 32], a
+ * mode outside [0, M), a mode named twice in a list: SUP_EINVAL with a message
+ * naming the place; on_cpu = 0 and n above SUP_TORONTONIAN_MAX_DEVICE_N:
+ * SUP_EUNSUPPORTED (the cap is 32: every n the entry takes); no device with
+ * on_cpu = 0: SUP_ENODEV (no CPU fallback).
+ * st: leaves = count, gray_steps = count 2^n, visited_steps = the subsets
+ * visited, kernel_ms, wall_ms, devices_used, grid, est_ops_per_step = fp64
+ * operations per subset (the census tor_ops(n) of DESIGN.md 8j). */
+#define SUP_TORONTONIAN_MAX_DEVICE_N 32
+int sup_torontonian(const double* O, int M, const int32_t* modes, int n, uint64_t count, const sup_opts* o, int on_cpu,
+                    double* out, sup_stats* st);
+/* One list, the subsets z in [z_begin, z_end) only.  A wave-chunk is
+ * 2^max(6, min(n, 9), n - 15) consecutive z; its partial adds its 64-aligned
+ * groups of signed f(z) in ascending order, and out[0] = the fold of the
+ * partials of the chunks the range touches, by the pairwise tree over (chunk -
+ * first chunk).  Ranges cut where such trees meet (aligned power-of-two runs
+ * of chunks) added pairwise in order reproduce the whole range's bits, and the
+ * whole range [0, 2^n) has sup_torontonian's bits; a cut inside a chunk agrees
+ * to rounding only.  z_begin > z_end or z_end > 2^n: SUP_EINVAL; an empty
+ * range: zero.  One device (o->device_id) or host threads; the other errors as
+ * above.  st: visited_steps = the subsets of the range, gray_steps = 2^n. */
+int sup_torontonian_range(const double* O, int M, const int32_t* modes, int n, uint64_t z_begin, uint64_t z_end,
+                          const sup_opts* o, int on_cpu, double* out, sup_stats* st);
+/* The subsets one list of n modes visits (2^n) and the census' fp64 operations
+ * per subset.  Host only; either output may be NULL.  n outside [1, 32]:
+ * SUP_EINVAL. */
+int sup_torontonian_plan(int n, uint64_t* subsets, double* est_ops);
 
 /* Nijenhuis-Wilf prologue (gpu_exact_dense.cu:642-652): x0[j] = a[j][n-1] - rowsum_j/2,
  * p0 = prod x0.  Host-only helper, exported for the test harness. */

@@ -24,6 +24,7 @@ __all__ = [
            "hafnian", "loop_hafnian", "hafnian_repeated", "hafnian_batch", "hafnian_plan",
            "hafnian_powertrace", "loop_hafnian_powertrace", "hafnian_powertrace_batch", "hafnian_powertrace_range",
            "hafnian_powertrace_plan", "HAFNIAN_PT_MAX_DEVICE_N",
+           "torontonian", "torontonian_batch", "torontonian_range", "torontonian_plan", "TORONTONIAN_MAX_DEVICE_N",
            "perman_complex_fock_minors_plan","perman_complex_minors", "perman_complex_minors_submatrices", "perman_complex_minors_range", "boson_sample", "read_mtx_complex", "partial", "perman_shard", "plan_info", "plan_census", "CENSUS_CLASSES", "plan_key", "prepare", "read_matrix", "read_mtx", "sort_order",
     "skip_order", "compress", "decompose", "perman_reduced", "approx", "grid_graph", "ALGOS_APPROX",
     "nw_start", "device_count", "rccl_devices", "layout", "ShardCall", "SupError", "ALGOS_DENSE", "ALGOS_SPARSE",
@@ -889,6 +890,85 @@ def hafnian_powertrace_plan(n: int, loop: bool = False):
     subsets, ops = C.c_uint64(0), C.c_double(0.0)
     _lib.check(_lib.load().sup_hafnian_complex_pt_plan(int(n), int(bool(loop)), C.byref(subsets), C.byref(ops)),
                "hafnian_powertrace_plan")
+    return int(subsets.value), float(ops.value)
+
+
+# include/superman.h SUP_TORONTONIAN_MAX_DEVICE_N: the largest number of modes
+# the torontonian kernel serves on the device (every n the entry takes)
+TORONTONIAN_MAX_DEVICE_N = 32
+
+
+def _tor_matrix(O):
+    o = np.ascontiguousarray(np.asarray(O, dtype=np.complex128))
+    if o.ndim != 2 or o.shape[0] != o.shape[1] or o.shape[0] < 2 or o.shape[0] % 2:
+        raise ValueError(f"expected a 2M x 2M matrix O with M >= 1, got shape {o.shape}")
+    return o
+
+
+def _tor_lists(modes):
+    i32 = np.ascontiguousarray(np.asarray(modes, dtype=np.int32))
+    single = i32.ndim == 1
+    if single:
+        i32 = i32[None, :]
+    if i32.ndim != 2 or i32.shape[1] < 1:
+        raise ValueError(f"modes must have shape [n] or [count, n] with n >= 1, got {np.shape(modes)}")
+    return np.ascontiguousarray(i32), int(i32.shape[0]), int(i32.shape[1]), single
+
+
+def torontonian_batch(O, modes, gpu_num: int = 1, device_id: int = 0, cpu: bool = False, threads: int = 16,
+                      return_stats: bool = False):
+    """The torontonians of the 2M x 2M Hermitian matrix ``O`` (thewalrus'
+    ordering: row i is mode i, row i + M its conjugate partner) on lists of
+    distinct modes (sup_torontonian): ``tor(O_s)`` with O_s the rows and columns
+    {s_b, s_b + M}.  ``modes`` has shape [n] (one result, a float) or [count, n]
+    (an array).  The kernel walk_tor.hip or (cpu=True) its host twin,
+    bit-identical.  Only the lower triangle of O and the real parts of its
+    diagonal are read; a list whose I - O_z is not positive definite for some
+    subset gives NaN."""
+    o = _tor_matrix(O)
+    i32, count, n, single = _tor_lists(modes)
+    lib = _lib.load()
+    op = _opts(gpu_num=gpu_num, device_id=device_id, threads=threads)
+    out, st = np.zeros(max(count, 1)), SupStats()
+    rc = lib.sup_torontonian(o.ctypes.data, o.shape[0] // 2, i32.ctypes.data, n, count, C.byref(op), int(bool(cpu)),
+                             out.ctypes.data, C.byref(st))
+    _lib.check(rc, "torontonian")
+    v = float(out[0]) if single else out[:count].copy()
+    return (v, st.as_dict()) if return_stats else v
+
+
+def torontonian(O, **kw):
+    """The torontonian of the whole 2M x 2M matrix O (``torontonian_batch``
+    with modes = 0..M-1), as thewalrus' ``tor``."""
+    return torontonian_batch(O, np.arange(np.shape(O)[0] // 2), **kw)
+
+
+def torontonian_range(O, modes, z_begin: int, z_end: int, device_id: int = 0, cpu: bool = False, threads: int = 16,
+                      return_stats: bool = False):
+    """The part of one list's torontonian sum from the subsets z in [z_begin,
+    z_end) (sup_torontonian_range): the chunk partials of the range folded
+    pairwise.  The whole range [0, 2^n) has ``torontonian_batch``'s bits."""
+    o = _tor_matrix(O)
+    i32, count, n, single = _tor_lists(modes)
+    if not single:
+        raise ValueError("torontonian_range takes one list of modes of shape [n]")
+    if not (0 <= int(z_begin) < 2**64 and 0 <= int(z_end) < 2**64):
+        raise ValueError("z_begin and z_end must be unsigned 64-bit integers")
+    lib = _lib.load()
+    op = _opts(gpu_num=1, device_id=device_id, threads=threads)
+    out, st = np.zeros(1), SupStats()
+    rc = lib.sup_torontonian_range(o.ctypes.data, o.shape[0] // 2, i32.ctypes.data, n, int(z_begin), int(z_end),
+                                   C.byref(op), int(bool(cpu)), out.ctypes.data, C.byref(st))
+    _lib.check(rc, "torontonian_range")
+    v = float(out[0])
+    return (v, st.as_dict()) if return_stats else v
+
+
+def torontonian_plan(n: int):
+    """(subsets, fp64 operations per subset) of one list of n modes
+    (sup_torontonian_plan, host only)."""
+    subsets, ops = C.c_uint64(0), C.c_double(0.0)
+    _lib.check(_lib.load().sup_torontonian_plan(int(n), C.byref(subsets), C.byref(ops)), "torontonian_plan")
     return int(subsets.value), float(ops.value)
 
 

@@ -45,6 +45,7 @@ EXPORTS = [
     "sup_perman_complex_fock_minors", "sup_perman_complex_fock_minors_plan", "sup_boson_sample_fock",
     "sup_hafnian_complex", "sup_loop_hafnian_complex", "sup_hafnian_complex_plan",
     "sup_hafnian_complex_pt", "sup_loop_hafnian_complex_pt", "sup_hafnian_complex_pt_range", "sup_hafnian_complex_pt_plan",
+    "sup_torontonian", "sup_torontonian_range", "sup_torontonian_plan",
     "sup_gpu_perman64_xshared_coalescing_mshared",
     "sup_gpu_perman64_xshared_coalescing_mshared_multigpu",
     "sup_gpu_perman64_xshared_coalescing_mshared_multigpucpu_chunks",
@@ -139,7 +140,7 @@ def load() -> C.CDLL:
             build()
         lib = C.CDLL(LIB_PATH)
         _declare(lib)
-        if lib.sup_abi_version() != 21:
+        if lib.sup_abi_version() != 22:
             raise RuntimeError("libsuperman_hip.so ABI version mismatch")
         _lib = lib
         return lib
@@ -202,6 +203,10 @@ def _declare(lib: C.CDLL) -> None:
     lib.sup_hafnian_complex_pt_range.argtypes = [P, I, P, P, I, C.c_uint64, C.c_uint64, C.POINTER(SupOpts), I, P,
                                                  C.POINTER(SupStats)]
     lib.sup_hafnian_complex_pt_plan.argtypes = [I, I, C.POINTER(C.c_uint64), C.POINTER(D)]
+    lib.sup_torontonian.argtypes = [P, I, P, I, C.c_uint64, C.POINTER(SupOpts), I, P, C.POINTER(SupStats)]
+    lib.sup_torontonian_range.argtypes = [P, I, P, I, C.c_uint64, C.c_uint64, C.POINTER(SupOpts), I, P,
+                                          C.POINTER(SupStats)]
+    lib.sup_torontonian_plan.argtypes = [I, C.POINTER(C.c_uint64), C.POINTER(D)]
     lib.sup_read_mtx_complex.argtypes = [C.c_char_p, C.POINTER(P), C.POINTER(I), C.POINTER(I)]
     lib.sup_perman_shard.argtypes = [P, I, I, I, I, I, C.POINTER(SupOpts), C.POINTER(D), C.POINTER(SupStats)]
     lib.sup_plan_info.argtypes = [P, I, I, I, C.POINTER(SupOpts), C.POINTER(I), P, C.POINTER(I), C.POINTER(I),

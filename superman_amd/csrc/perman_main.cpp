@@ -45,6 +45,10 @@
 // --hafnian --powertrace: the same value through sup_hafnian_complex_pt /
 // sup_loop_hafnian_complex_pt (2^(n/2) subsets instead of 2^(n-1) states; on
 // the device up to n = SUP_HAFNIAN_PT_MAX_DEVICE_N, with -c up to 64).
+// --torontonian [--modes 0,3,5]: sup_torontonian of a 2M x 2M Hermitian
+// MatrixMarket `complex` file (thewalrus' ordering) on the listed distinct
+// modes (default: all M); prints "Torontonian: <value>".  -g the device
+// kernel, -c the host threads.
 #include <getopt.h>
 
 #include <chrono>
@@ -64,7 +68,7 @@ struct Cli {
   bool generic = true, dense = true, approximation = false, gpu = false, cpu = false, grid_graph = false;
   bool rccl = false, verbose = false, compression = false, exact = false, quad = false;
   bool half_calc = false, half_store = false, complex = false, complex_quad = false, complex_exact = false, preprocessing_given = false, gpu_num_given = false;
-  bool hafnian = false, loop = false, powertrace = false;
+  bool hafnian = false, loop = false, powertrace = false, torontonian = false;
   int gpu_num = 2, threads = 16, perman_algo = 1, preprocessing = 0, device = 0, reps = 1;
   double scaling = -1.0;
   long number_of_times = 100000;  // main.cu:338-344 defaults
@@ -72,6 +76,7 @@ struct Cli {
   unsigned long long seed = 1;
   int jit = 0;
   std::string filename, checkpoint, rpt;
+  std::string modes;
 };
 
 int fail(const char* what) {
@@ -283,6 +288,74 @@ int run_hafnian_cli(const Cli& c) {
   return 0;
 }
 
+// --torontonian: sup_torontonian of a Hermitian MatrixMarket `complex` file of
+// even order; the line shape follows --hafnian.
+int run_torontonian_cli(const Cli& c) {
+  const struct {
+    bool on;
+    const char* opt;
+  } refused[] = {{!c.dense, "-s"},       {c.compression, "-o"},    {c.scaling > 0.0, "-u"},
+                 {c.exact, "-E"},        {c.quad, "-q"},           {c.approximation, "-a"},
+                 {!c.generic, "-b"},     {c.grid_graph, "-i"},     {c.preprocessing_given, "-r"},
+                 {c.complex, "--complex"}, {c.complex_quad, "--complex-quad"}, {c.complex_exact, "--complex-exact"},
+                 {c.hafnian, "--hafnian"}, {c.loop, "--loop"}, {!c.rpt.empty(), "--rpt"}, {c.powertrace, "--powertrace"}};
+  for (const auto& r : refused)
+    if (r.on) {
+      std::fprintf(stderr, "perman: --torontonian does not combine with %s\n", r.opt);
+      return 1;
+    }
+  double* mat = nullptr;
+  int N = 0, nnz = 0;
+  if (sup_read_mtx_complex(c.filename.c_str(), &mat, &N, &nnz) != SUP_OK) return fail("reading complex matrix");
+  if (N < 2 || (N & 1)) {
+    std::fprintf(stderr, "perman: --torontonian needs a matrix of even order 2M (got %d)\n", N);
+    sup_free(mat);
+    return 1;
+  }
+  const int M = N / 2;
+  std::vector<int32_t> modes;
+  if (c.modes.empty()) {
+    for (int k = 0; k < M; ++k) modes.push_back(k);
+  } else {
+    for (const char* p = c.modes.c_str(); *p;) {
+      char* end = nullptr;
+      const long r = std::strtol(p, &end, 10);
+      if (end == p || r < 0 || r >= M || (*end && *end != ',') || modes.size() >= 32) {
+        std::fprintf(stderr, "perman: --modes takes at most 32 comma-separated modes in [0, %d)\n", M);
+        sup_free(mat);
+        return 1;
+      }
+      modes.push_back((int32_t)r);
+      p = *end ? end + 1 : end;
+    }
+  }
+  if (modes.empty() || modes.size() > 32) {
+    std::fprintf(stderr, "perman: --torontonian needs 1 to 32 modes (got %zu)\n", modes.size());
+    sup_free(mat);
+    return 1;
+  }
+  sup_opts o;
+  sup_opts_init(&o);
+  o.gpu_num = 1;
+  o.device_id = c.device;
+  o.threads = c.threads;
+  double out = 0.0;
+  sup_stats st;
+  int rc = SUP_OK;
+  const auto t0 = std::chrono::steady_clock::now();
+  for (int rep = 0; rep < c.reps && rc == SUP_OK; ++rep)
+    rc = sup_torontonian(mat, M, modes.data(), (int)modes.size(), 1, &o, c.gpu ? 0 : 1, &out, &st);
+  const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / (double)c.reps;
+  sup_free(mat);
+  if (rc != SUP_OK) return fail("torontonian");
+  std::cout << "Result: " << (c.gpu ? "gpu_" : "cpu_") << "torontonian64 " << out << " in " << sec << std::endl;
+  std::printf("Torontonian: %.17e\n", out);
+  if (c.verbose)
+    std::printf("Stats: devices %d kernel_ms %.3f wall_ms %.3f subsets %llu grid %d\n", st.devices_used, st.kernel_ms,
+                st.wall_ms, (unsigned long long)st.visited_steps, st.grid);
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -310,6 +383,8 @@ int main(int argc, char** argv) {
                                         {"loop", 0, NULL, 1004},
                                         {"rpt", 1, NULL, 1005},
                                         {"powertrace", 0, NULL, 1006},
+                                        {"torontonian", 0, NULL, 1007},
+                                        {"modes", 1, NULL, 1008},
                                         {NULL, 0, NULL, 0}};
   int opt;
   auto need_arg = [&](char o) -> bool {
@@ -352,6 +427,8 @@ int main(int argc, char** argv) {
       case 1004: c.loop = true; break;
       case 1005: c.rpt = optarg; break;
       case 1006: c.powertrace = true; break;
+      case 1007: c.torontonian = true; break;
+      case 1008: c.modes = optarg; break;
       case 'v': c.verbose = true; break;
       // v2 flags (revised_perman/main.cpp:1431-1460): -w stores the matrix in
       // single precision (the permanent of the float-rounded entries); -h asks
@@ -379,6 +456,11 @@ int main(int argc, char** argv) {
   }
   for (int i = optind; i < argc; ++i) std::printf("Non-option argument %s\n", argv[i]);
   if (!c.cpu && !c.gpu) c.gpu = true;  // main.cu:482-484
+  if (c.torontonian) return run_torontonian_cli(c);
+  if (!c.modes.empty()) {
+    std::fprintf(stderr, "perman: --modes goes with --torontonian\n");
+    return 1;
+  }
   if (c.hafnian) return run_hafnian_cli(c);
   if (c.powertrace) {
     std::fprintf(stderr, "perman: --powertrace goes with --hafnian\n");

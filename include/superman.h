@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SUP_ABI_VERSION 22  /* 22: sup_torontonian, sup_torontonian_range, sup_torontonian_plan, SUP_TORONTONIAN_MAX_DEVICE_N; 21: sup_hafnian_complex_pt, sup_loop_hafnian_complex_pt, sup_hafnian_complex_pt_range, sup_hafnian_complex_pt_plan, SUP_HAFNIAN_PT_MAX_DEVICE_N; 20: sup_hafnian_complex, sup_loop_hafnian_complex, sup_hafnian_complex_plan; 19: sup_perman_complex_exact, sup_perman_complex_exact_range, SUP_CPLX_EXACT_MAX_DEVICE_N; 18: sup_perman_complex_quad, sup_perman_complex_quad_range, SUP_CPLX_QUAD_MAX_DEVICE_N; 17:sup_perman_complex_fock_minors, sup_perman_complex_fock_minors_plan, sup_boson_sample_fock; 16: sup_plan_census; 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
+#define SUP_ABI_VERSION 23  /* 23: sup_hafnian_complex_exact; 22: sup_torontonian, sup_torontonian_range, sup_torontonian_plan, SUP_TORONTONIAN_MAX_DEVICE_N; 21: sup_hafnian_complex_pt, sup_loop_hafnian_complex_pt, sup_hafnian_complex_pt_range, sup_hafnian_complex_pt_plan, SUP_HAFNIAN_PT_MAX_DEVICE_N; 20: sup_hafnian_complex, sup_loop_hafnian_complex, sup_hafnian_complex_plan; 19: sup_perman_complex_exact, sup_perman_complex_exact_range, SUP_CPLX_EXACT_MAX_DEVICE_N; 18: sup_perman_complex_quad, sup_perman_complex_quad_range, SUP_CPLX_QUAD_MAX_DEVICE_N; 17:sup_perman_complex_fock_minors, sup_perman_complex_fock_minors_plan, sup_boson_sample_fock; 16: sup_plan_census; 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SUP_OK            0
@@ -727,6 +727,48 @@ int sup_loop_hafnian_complex(const double* A, int M, const double* mu, const int
 /* The terms T of each matrix's sum, host only (no device).  terms may be NULL.
  * A null list or n outside [1, 64]: SUP_EINVAL.  Indices are only compared. */
 int sup_hafnian_complex_plan(const int32_t* idx, int n, uint64_t count, uint64_t* terms);
+
+/* Exact hafnians and loop hafnians of Gaussian-integer matrices (ABI 23): the
+ * integer truth the floating hafnian entries are judged against, and exact
+ * counts of (weighted) perfect matchings.  A, idx, n, count and the gathers as
+ * sup_hafnian_complex; mu NULL: the plain hafnian, else the loop hafnian.
+ * Every part of A and mu must be an integer with |part| < 2^31.  With the
+ * integers H_k = s_k - 2 v_k, q' = H^T Abar H, r' = mubar . H, m = floor(n/2),
+ *   T = sum_v (-1)^(sum v) prod C(s'_k, v_k) q'^m               haf  = 2 T / (m! 8^m)
+ *   L = sum_v (...) sum_{j <= m} c_j q'^j r'^(n-2j)              lhaf = 2 L / (n! 2^(n+m))
+ *   c_j = n! / (j! (n-2j)!) 2^(m-j)
+ * over the same multiplicity vectors, layout and Gray order as
+ * sup_hafnian_complex.  q', r' and the step are exact in fp64;
+ * the power, the polynomial and every weight are formed in (Z/p)[i] for primes
+ * p < 2^25 (residue times residue: 2.25 p^2 < 2^52, hafexact.hpp), taken until
+ * their product exceeds 8 times the bound 2^(n-1) R^m (plain) or 2^(n-1) sum_j
+ * c_j R^j R_mu^(n-2j) (loop), R, R_mu = the sums of |Re| + |Im| over the
+ * gathered matrix and mu (the largest over the call's matrices).  The residues
+ * of Re and Im are joined separately by CRT; 2T must be divisible by m! 8^m
+ * and 2L by n! 2^(n+m): a built-in self-check (a failure is SUP_EHIP with a
+ * message, never a wrong number).  Plain form, odd n: "0", "0", nothing walked.
+ * The device walk (walk_hafexact.hip) serves every n <= 64, kHafxPrimes primes
+ * per launch (hafexact.hpp; more primes take more launches over the same tables);
+ * on_cpu = 1 runs the same residue operations on o->threads host threads, and
+ * the two agree residue for residue.  o->gpu_num devices take contiguous
+ * ranges of matrices.
+ * Result k: signed decimal integers, NUL-terminated, at out_re + k out_len and
+ * out_im + k out_len; a buffer too short for a result is SUP_EINVAL with the
+ * length needed in the message (768 bytes always suffice).
+ * Errors, all before any device work and in this order: a null pointer, n
+ * outside [1, 64], M < 1, a pair A[i][j], A[j][i] that differs, an index
+ * outside [0, M), a part of A or mu that is not an integer or has |part| >=
+ * 2^31: SUP_EINVAL with a message naming the place (row, column, part); a
+ * matrix of more than 2^24 wave-chunks: SUP_EUNSUPPORTED; no device with
+ * on_cpu = 0: SUP_ENODEV (no CPU fallback).
+ * st: leaves = count, gray_steps = count 2^(n-1) (nominal), visited_steps =
+ * sum_k T_k, kernel_ms, wall_ms, devices_used, grid, seg_cached_bits = the
+ * primes of the call, seg_pair_bits = the walk launches of a slab,
+ * est_ops_per_step = the census hafx_ops (fp64 instructions per
+ * state and lane summed over the launches, T-weighted mean over the matrices). */
+int sup_hafnian_complex_exact(const double* A, int M, const double* mu /* NULL: plain hafnian */, const int32_t* idx,
+                              int n, uint64_t count, const sup_opts* o, int on_cpu, char* out_re, char* out_im,
+                              size_t out_len /* per matrix */, sup_stats* st);
 
 /* Power-trace hafnians and loop hafnians (ABI 21): the same gathers and the
  * same mathematical values as sup_hafnian_complex / sup_loop_hafnian_complex by

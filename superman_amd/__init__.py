@@ -22,6 +22,7 @@ from ._lib import (KERNEL_DENSE, KERNEL_SKIPPER, KERNEL_SPARYSER, LEAF_FN, SCHED
 __all__ = [
     "perman", "perman_cpu", "perman_exact", "perman_exact_range", "perman_quad", "perman_quad_range", "perman_complex", "perman_complex_range", "perman_complex_quad", "perman_complex_quad_range", "COMPLEX_QUAD_MAX_DEVICE_N", "perman_complex_exact", "perman_complex_exact_range", "COMPLEX_EXACT_MAX_DEVICE_N", "perman_complex_batch", "perman_complex_submatrices", "perman_complex_fock", "perman_complex_fock_plan", "perman_complex_fock_minors", "perman_complex_fock_minors_submatrices",
            "hafnian", "loop_hafnian", "hafnian_repeated", "hafnian_batch", "hafnian_plan",
+           "hafnian_exact", "loop_hafnian_exact", "hafnian_exact_repeated", "hafnian_exact_batch",
            "hafnian_powertrace", "loop_hafnian_powertrace", "hafnian_powertrace_batch", "hafnian_powertrace_range",
            "hafnian_powertrace_plan", "HAFNIAN_PT_MAX_DEVICE_N",
            "torontonian", "torontonian_batch", "torontonian_range", "torontonian_plan", "TORONTONIAN_MAX_DEVICE_N",
@@ -803,6 +804,76 @@ def hafnian_plan(idx):
     terms = np.zeros(max(count, 1), np.uint64)
     _lib.check(_lib.load().sup_hafnian_complex_plan(i32.ctypes.data, n, count, terms.ctypes.data), "hafnian_plan")
     return int(terms[0]) if single else terms[:count].copy()
+
+
+def _haf_exact_parts(x, what: str, name: str) -> np.ndarray:
+    """`x` as a C-order complex128 array for the exact hafnian entry
+    (``_cmat_exact``'s rule): an integer complex128 cannot hold exactly is
+    refused here with its place, not rounded; integrality and range of what
+    float and complex arrays hold are the library's checks."""
+    raw = np.asarray(x)
+    if raw.dtype.kind in "iuO":
+        for idx, v in np.ndenumerate(raw):
+            if isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) and abs(int(v)) >= 1 << 53:
+                raise SupError(-1, what, f"{name} entry {idx} = {int(v)} is not exactly representable in fp64 "
+                                         "(parts must be integers with |part| < 2^31)")
+    return np.ascontiguousarray(np.asarray(raw, dtype=np.complex128))
+
+
+def hafnian_exact_batch(A, idx, mu=None, loop: bool = False, gpu_num: int = 1, device_id: int = 0, cpu: bool = False,
+                        threads: int = 16, return_stats: bool = False):
+    """The exact hafnians (``loop=True``: loop hafnians) of the gathers
+    ``A[np.ix_(idx[k], idx[k])]`` of a symmetric matrix of Gaussian integers
+    (sup_hafnian_complex_exact): ``hafnian_batch``'s sum over the multiplicity
+    vectors on integers, in residue arithmetic over (Z/p)[i] for primes below
+    2^25 (walk_hafexact.hip, or (cpu=True) its host twin: the same integers),
+    joined by CRT.  Parts of A and mu must be integers with |part| < 2^31;
+    ``mu`` defaults to the diagonal of A in the loop form.  A list of shape [n]
+    gives ``(re, im)``, two Python ints; of shape [count, n] a list of such
+    pairs.  It is the truth ``hafnian``, ``loop_hafnian`` and
+    ``hafnian_powertrace`` are judged against, and counts perfect matchings."""
+    what = "loop_hafnian_exact" if loop else "hafnian_exact"
+    a = _haf_exact_parts(A, what, "A")
+    if a.ndim != 2 or a.shape[0] != a.shape[1] or a.shape[0] < 1:
+        raise ValueError(f"expected a non-empty square matrix A, got shape {a.shape}")
+    m = None
+    if loop:
+        m = np.ascontiguousarray(np.diag(a)) if mu is None else _haf_exact_parts(mu, what, "mu")
+        if m.shape != (a.shape[0],):
+            raise ValueError(f"mu must have shape [{a.shape[0]}], got {m.shape}")
+    i32, count, n, single = _haf_lists(idx)
+    lib = _lib.load()
+    o = _opts(gpu_num=gpu_num, device_id=device_id, threads=threads)
+    ln = 768
+    re, im, st = C.create_string_buffer(ln * max(count, 1)), C.create_string_buffer(ln * max(count, 1)), SupStats()
+    rc = lib.sup_hafnian_complex_exact(a.ctypes.data, a.shape[0], m.ctypes.data if loop else None, i32.ctypes.data, n,
+                                       count, C.byref(o), int(bool(cpu)), re, im, ln, C.byref(st))
+    _lib.check(rc, what)
+    rb, ib = re.raw, im.raw
+    v = [(int(rb[k * ln:rb.index(b"\0", k * ln)]), int(ib[k * ln:ib.index(b"\0", k * ln)])) for k in range(count)]
+    v = v[0] if single else v
+    return (v, st.as_dict()) if return_stats else v
+
+
+def hafnian_exact(A, **kw):
+    """The exact hafnian of the whole symmetric Gaussian-integer matrix A as
+    ``(re, im)`` (``hafnian_exact_batch`` with idx = 0..n-1)."""
+    return hafnian_exact_batch(A, np.arange(np.shape(A)[0]), **kw)
+
+
+def loop_hafnian_exact(A, mu=None, **kw):
+    """The exact loop hafnian of the whole matrix A; ``mu`` defaults to its diagonal."""
+    return hafnian_exact_batch(A, np.arange(np.shape(A)[0]), mu=mu, loop=True, **kw)
+
+
+def hafnian_exact_repeated(A, rpt, mu=None, loop: bool = False, **kw):
+    """The exact (loop) hafnian of A with mode k taken ``rpt[k]`` times (zeros
+    allowed): ``hafnian_exact_batch`` on the list that repeats k rpt[k] times."""
+    r = np.asarray(rpt)
+    if (r.ndim != 1 or r.shape[0] != np.shape(A)[0] or (r.size and not np.issubdtype(r.dtype, np.integer))
+            or (r < 0).any()):
+        raise ValueError(f"rpt must hold one non-negative integer per mode of A, got {rpt!r}")
+    return hafnian_exact_batch(A, np.repeat(np.arange(r.shape[0]), r), mu=mu, loop=loop, **kw)
 
 
 # include/superman.h SUP_HAFNIAN_PT_MAX_DEVICE_N: the largest order the

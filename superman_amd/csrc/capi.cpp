@@ -7,6 +7,7 @@
 
 #include "dd.hpp"
 #include "engine.hpp"
+#include "hafnian_exact.hpp"
 #include "hafnian_pt.hpp"
 #include "torontonian.hpp"
 
@@ -654,6 +655,50 @@ int sup_loop_hafnian_complex(const double* A, int M, const double* mu, const int
 
 int sup_hafnian_complex_plan(const int32_t* idx, int n, uint64_t count, uint64_t* terms) {
   return hafnian_plan(idx, n, count, terms);
+}
+
+int sup_hafnian_complex_exact(const double* A, int M, const double* mu, const int32_t* idx, int n, uint64_t count,
+                              const sup_opts* o_in, int on_cpu, char* out_re, char* out_im, size_t out_len,
+                              sup_stats* st) {
+  auto t0 = std::chrono::steady_clock::now();
+  if (!A || !idx || ((!out_re || !out_im) && count > 0)) {
+    set_error("sup_hafnian_complex_exact: null pointer");
+    return SUP_EINVAL;
+  }
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  HafIn in;
+  in.A = A, in.M = M, in.mu = mu, in.idx = idx, in.loop = mu != nullptr;
+  std::vector<std::string> re, im;
+  HafxInfo hi;
+  if (int rc = hafnian_exact(in, n, count, o, on_cpu != 0, re, im, &hi)) return rc;
+  size_t need = 0;
+  for (uint64_t k = 0; k < count; ++k) need = std::max(need, std::max(re[k].size(), im[k].size()) + 1);
+  if (out_len < need) {
+    set_error("sup_hafnian_complex_exact: out_len = " + std::to_string(out_len) + " but a result needs " +
+              std::to_string(need) + " bytes per matrix and buffer (768 always suffice)");
+    return SUP_EINVAL;
+  }
+  for (uint64_t k = 0; k < count; ++k) {
+    std::memcpy(out_re + k * out_len, re[k].c_str(), re[k].size() + 1);
+    std::memcpy(out_im + k * out_len, im[k].c_str(), im[k].size() + 1);
+  }
+  if (st) {
+    std::memset(st, 0, sizeof(*st));
+    st->kernel_ms = hi.kernel_ms;
+    st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    st->gray_steps = count << (n - 1);  // nominal: the sum without repeats
+    st->visited_steps = hi.terms;
+    st->devices_used = hi.devices;
+    st->grid = hi.grid;
+    st->walk_kind = (int)kWalkDense;
+    st->leaves = (int)std::min<uint64_t>(count, 0x7fffffffu);
+    st->est_ops_per_step = hi.ops;
+    st->seg_cached_bits = (int16_t)hi.primes;
+    st->seg_pair_bits = (int16_t)hi.launches;
+  }
+  return SUP_OK;
 }
 
 static int hafnian_pt_entry(const HafIn& in, int n, uint64_t count, bool range, uint64_t z0, uint64_t z1,

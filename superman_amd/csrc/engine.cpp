@@ -3,6 +3,7 @@
 // (run_range, run_range_batch, run_range_exact, run_range_dd, warm_devices).
 // Plans come from plan.cpp; the schedulers that call these are schedule.cpp.
 #include "engine.hpp"
+#include "hafnian_exact.hpp"
 #include "hafnian_pt.hpp"
 #include "torontonian.hpp"
 
@@ -1487,6 +1488,110 @@ int run_hafnian(int dev, const HafSlab& S, const HafIn& in, double* out, double*
   SUP_HIP(hipMemcpyAsync(out, c->d_cbout, (size_t)(K * 2) * sizeof(double), hipMemcpyDeviceToHost, s));
   if (grid_out) *grid_out = (int)geo.grid;
   return timed_sync(c, kernel_ms);
+}
+
+// Exact hafnian walk (walk_hafexact.hip) of slab S on device `dev`, as
+// run_hafnian's: A, mu and the slab's descriptor pools go up and prepare writes
+// the integer tables once; then, per launch of at most kHafxPrimes primes,
+// those primes' blocks of ptab go up, the walk runs over the slab's queue and
+// the per-matrix fold leaves 16 kHafxPrimes bytes per matrix, which one
+// download brings back.  The buffers are the collision-aware walk's (same
+// context lock).  A launch's kernels are timed by the context's event pair.
+int run_hafnian_exact(int dev, const HafSlab& S, const HafIn& in, const std::vector<double>& primes,
+                      const std::vector<double>& ptab, uint64_t* res, double* kernel_ms, int* grid_out,
+                      int* launches_out) {
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (grid_out) *grid_out = 0;
+  if (launches_out) *launches_out = 0;
+  const uint64_t K = S.mats.size(), chunks = S.chunks.size();
+  if (K == 0) return SUP_OK;
+  const size_t np = primes.size();
+  const uint64_t stride = hafx_stride(S.prog.size());
+  if (S.n < 1 || S.n > SUP_MAX_N || (!S.loop && (S.n & 1)) || chunks == 0 || chunks > 0x7fffffffull || !res || !in.A ||
+      in.M < 1 || (S.loop && !in.mu) || np == 0 || ptab.size() != np * stride ||
+      stride * 8 * (uint64_t)kHafxPrimes > 0xffffffffull) {
+    set_error("run_hafnian_exact: bad request");
+    return SUP_EINVAL;
+  }
+  // the packed pools, each starting on a 16-byte unit
+  auto units = [](size_t bytes) { return (bytes + 15) / 16; };
+  const size_t u_prog = 0, u_dig = u_prog + units(S.prog.size() * sizeof(HafStep));
+  const size_t u_mats = u_dig + units(S.dig.size() * sizeof(HafDigit));
+  const size_t u_chunks = u_mats + units(K * sizeof(HafMat));
+  const size_t u_grp = u_chunks + units(chunks * sizeof(FockChunk));
+  const size_t u_ptab = (u_grp + units(S.grp.size() * sizeof(int32_t)) + 3) / 4 * 4;  // on 64 bytes
+  const size_t u_end = u_ptab + units((size_t)kHafxPrimes * stride * sizeof(double)) + 1;
+  const size_t a_doubles = (size_t)2 * in.M * in.M, mu_doubles = S.loop ? (size_t)2 * in.M : 0;
+  constexpr size_t per = 2 * (size_t)kHafxPrimes;  // doubles per wave-chunk and per matrix of a launch
+  CtxGuard guard;
+  int rc = guard.open(dev, "device buffers");
+  if (rc) return rc;
+  DeviceCtx* c = guard.c;
+  int occ = 0;
+  SUP_HIP(hafexact_occupancy(S.loop, &occ));
+  if ((rc = ensure(c->d_cbtab, c->cbtab_cap, (size_t)S.tab_doubles))) return rc;
+  if ((rc = ensure(c->d_cbU, c->cbU_cap, a_doubles + mu_doubles))) return rc;
+  if ((rc = ensure(c->d_chunk, c->chunk_cap, (size_t)chunks * per))) return rc;
+  if ((rc = ensure(c->d_cbout, c->cbout_cap, (size_t)K * per))) return rc;
+  if ((rc = ensure(c->d_fock, c->fock_cap, u_end))) return rc;
+  hipStream_t s = c->stream;
+  c->tables_uid = 0;  // the walk leaves head 0 nonzero
+  c->head_zero[0] = false;
+  auto up = [&](void* dst, const void* src, size_t bytes) {
+    return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+  };
+  SUP_HIP(up(c->d_cbU, in.A, a_doubles * sizeof(double)));
+  SUP_HIP(up(c->d_cbU + a_doubles, in.mu, mu_doubles * sizeof(double)));
+  SUP_HIP(up(c->d_fock + u_grp, S.grp.data(), S.grp.size() * sizeof(int32_t)));
+  SUP_HIP(up(c->d_fock + u_prog, S.prog.data(), S.prog.size() * sizeof(HafStep)));
+  SUP_HIP(up(c->d_fock + u_dig, S.dig.data(), S.dig.size() * sizeof(HafDigit)));
+  SUP_HIP(up(c->d_fock + u_mats, S.mats.data(), K * sizeof(HafMat)));
+  SUP_HIP(up(c->d_fock + u_chunks, S.chunks.data(), chunks * sizeof(FockChunk)));
+  const uint64_t resident = (uint64_t)c->cus * (uint64_t)std::max(occ, 1);
+  const char* fg = std::getenv("SUP_WALK_GROUP");  // tests, read per call: chunks per ticket (the residues do not change)
+  const LaunchGeom geo = walk_geometry(chunks, resident, kWavesPerBlock, false, fg ? std::max(1, std::atoi(fg)) : 0);
+  HafxParams p{};
+  p.tabs = c->d_cbtab;
+  p.prog = reinterpret_cast<const HafStep*>(c->d_fock + u_prog);
+  p.dig = reinterpret_cast<const HafDigit*>(c->d_fock + u_dig);
+  p.mats = reinterpret_cast<const HafMat*>(c->d_fock + u_mats);
+  p.chunks = reinterpret_cast<const FockChunk*>(c->d_fock + u_chunks);
+  p.ptab = reinterpret_cast<const double*>(c->d_fock + u_ptab);
+  p.chunk_count = chunks;
+  p.chunk_out = c->d_chunk;
+  p.counter = c->d_counter;
+  p.group = geo.group;
+  p.n = (unsigned)S.n;
+  p.stride = (unsigned)stride;
+  std::vector<double> sums((size_t)K * per);
+  for (size_t q0 = 0; q0 < np; q0 += (size_t)kHafxPrimes) {
+    const size_t nq = std::min(np - q0, (size_t)kHafxPrimes);
+    p.nprimes = (unsigned)nq;
+    SUP_HIP(up(c->d_fock + u_ptab, ptab.data() + q0 * stride, nq * stride * sizeof(double)));
+    SUP_HIP(hipMemsetAsync(c->d_counter, 0, sizeof(unsigned), s));
+    SUP_HIP(hipEventRecord(c->ev0, s));
+    SUP_ON_DEVICE(c->dev, "exact hafnian walk launch");
+    if (q0 == 0)
+      SUP_HIP(launch_hafexact_prepare(c->d_cbU, in.M, S.loop ? c->d_cbU + a_doubles : nullptr,
+                                      reinterpret_cast<const int32_t*>(c->d_fock + u_grp), p.mats, K, c->d_cbtab, s));
+    SUP_HIP(launch_hafexact(S.loop, p, (int)geo.grid, s));
+    SUP_HIP(launch_hafexact_fold(c->d_chunk, p.mats, K, (uint32_t)nq, c->d_cbout, s));
+    SUP_HIP(hipEventRecord(c->ev1, s));
+    SUP_HIP(hipMemcpyAsync(sums.data(), c->d_cbout, sums.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    double ms = 0.0;
+    if ((rc = timed_sync(c, &ms))) return rc;
+    if (kernel_ms) *kernel_ms += ms;
+    if (launches_out) ++*launches_out;
+    // a matrix's sum of chunk residues is an exact integer below 2^49
+    for (uint64_t k = 0; k < K; ++k)
+      for (size_t q = 0; q < nq; ++q) {
+        const uint64_t pq = (uint64_t)primes[q0 + q];
+        res[(k * np + q0 + q) * 2] = (uint64_t)sums[k * per + 2 * q] % pq;
+        res[(k * np + q0 + q) * 2 + 1] = (uint64_t)sums[k * per + 2 * q + 1] % pq;
+      }
+  }
+  if (grid_out) *grid_out = (int)geo.grid;
+  return SUP_OK;
 }
 
 // Power-trace hafnian kernel (walk_hafpt.hip) on matrices [first, first + K) of

@@ -457,6 +457,18 @@ void exact_take_primes(int pbits, double bits, std::vector<double>& primes);
 // string.  T not divisible by 2^(n-1): SUP_EHIP, the message starting with `who`.
 int exact_crt_perman(const std::vector<double>& primes, const std::vector<uint64_t>& res, int n, const char* who,
                      std::string& out);
+// The same join with the divisor as an argument: out = (negate ? -1 : 1) mul T /
+// (2^shift fact!) as a signed decimal string.  mul T not divisible by it:
+// SUP_EHIP, "<who>: self-check failed (<what>)".  exact_crt_perman is this with
+// mul = 1, shift = n - 1, fact = 1, negate = n even.
+struct ExactDivisor {
+  uint32_t mul = 1;
+  int shift = 0;
+  int fact = 1;
+  bool negate = false;
+};
+int exact_crt_div(const std::vector<double>& primes, const std::vector<uint64_t>& res, const ExactDivisor& d,
+                  const char* who, const char* what, std::string& out);
 // n in [1, 64], o.walk_log2 in [0, 31] and form in [0, 2] of a range entry
 // (`who` in the messages), else SUP_EINVAL.
 int check_range_request(int n, const sup_opts& o, int form, const char* who);
@@ -759,5 +771,15 @@ int hafnian_complex(const HafIn& in, int n, uint64_t count, const sup_opts& o, b
                     HafInfo* info);
 // Per matrix the terms T of its sum (sup_hafnian_complex_plan).  Host only.
 int hafnian_plan(const int32_t* idx, int n, uint64_t count, uint64_t* terms);
+// The checks of n, M, the symmetry of A and the indices that every Kan-walk
+// hafnian entry makes, in this order (`who` in the messages): SUP_EINVAL or 0.
+int haf_check_request(const HafIn& in, int n, uint64_t count, const std::string& who);
+// The slab builder of hafnian_complex, shared with hafnian_exact.cpp: appends
+// matrices k, k + 1, .. < kend of in.idx (order n) to the empty slab S while it
+// stays under the slab cap in bytes (partial_bytes per wave-chunk of partials),
+// 2^31 chunks and slab_max matrices (at least one is taken), and returns the
+// first matrix not taken.  host_tables: write haf_entry's tables into S.tabs.
+uint64_t haf_fill_slab(HafSlab& S, const HafIn& in, int n, uint64_t k, uint64_t kend, uint64_t slab_max,
+                       size_t partial_bytes, bool host_tables);
 
 }  // namespace sup

@@ -270,10 +270,11 @@ void exact_take_primes(int pbits, double bits, std::vector<double>& primes) {
 }
 
 // The residues res[i] in [0, primes[i]) of an integer T with |T| < (prod p) / 2
-// joined by CRT, and out = (4(n&1) - 2) T / 2^n as a signed decimal string.  T
-// must be divisible by 2^(n-1) (the walk's self-check): else SUP_EHIP.
-int exact_crt_perman(const std::vector<double>& primes, const std::vector<uint64_t>& res, int n, const char* who,
-                     std::string& out) {
+// joined by CRT, and out = (d.negate ? -1 : 1) d.mul T / (2^d.shift d.fact!) as
+// a signed decimal string.  d.mul T must be divisible by the divisor (the
+// walks' self-check): else SUP_EHIP, "<who>: self-check failed (<what>)".
+int exact_crt_div(const std::vector<double>& primes, const std::vector<uint64_t>& res, const ExactDivisor& d,
+                  const char* who, const char* what, std::string& out) {
   const int np = (int)primes.size();
   // Garner: mixed-radix digits v_i, then T = sum v_i prod_{j<i} p_j in [0, M)
   std::vector<uint64_t> p(np), v(np);
@@ -303,15 +304,34 @@ int exact_crt_perman(const std::vector<double>& primes, const std::vector<uint64
     T = t;
     neg = true;
   }
-  // perm = (4(n&1) - 2) T / 2^n = (n odd ? 1 : -1) T / 2^(n-1)
-  if (!T.low_bits_zero(n - 1)) {
-    set_error(std::string(who) + ": self-check failed (T not divisible by 2^(n-1))");
+  if (d.mul != 1) T.mul_add(d.mul, 0);
+  bool divides = T.low_bits_zero(d.shift);
+  if (divides) {
+    T.shr(d.shift);
+    // f! divides T exactly when 2, 3, .., f divide the successive quotients
+    for (int f = 2; f <= d.fact && divides; ++f) {
+      Big q = T;
+      if (q.divmod((uint32_t)f) != 0) divides = false;
+      else T = q;
+    }
+  }
+  if (!divides) {
+    set_error(std::string(who) + ": self-check failed (" + what + ")");
     return SUP_EHIP;
   }
-  T.shr(n - 1);
-  if (!(n & 1)) neg = !neg;
+  if (d.negate) neg = !neg;
   out = (neg && !T.zero() ? "-" : "") + T.dec();
   return SUP_OK;
+}
+
+// perm = (4(n&1) - 2) T / 2^n = (n odd ? 1 : -1) T / 2^(n-1): T must be
+// divisible by 2^(n-1).
+int exact_crt_perman(const std::vector<double>& primes, const std::vector<uint64_t>& res, int n, const char* who,
+                     std::string& out) {
+  ExactDivisor d;
+  d.shift = n - 1;
+  d.negate = !(n & 1);
+  return exact_crt_div(primes, res, d, who, "T not divisible by 2^(n-1)", out);
 }
 
 int check_range_request(int n, const sup_opts& o, int form, const char* who) {

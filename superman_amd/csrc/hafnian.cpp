@@ -45,10 +45,11 @@ HafChoice haf_choose(const int32_t* idx, int n) {
   return c;
 }
 
-// Bytes a matrix adds to a slab (table, partials, descriptors).
-size_t haf_bytes(const HafChoice& c) {
+// Bytes a matrix adds to a slab (table, partials of partial_bytes per
+// wave-chunk, descriptors).
+size_t haf_bytes(const HafChoice& c, size_t partial_bytes) {
   const size_t chunks = (size_t)((c.lay.H + 63) / 64);
-  return (size_t)haf_pairs(c.lay.nwalk, c.lay.nd - c.lay.nwalk) * 16 + chunks * (sizeof(FockChunk) + 16) +
+  return (size_t)haf_pairs(c.lay.nwalk, c.lay.nd - c.lay.nwalk) * 16 + chunks * (sizeof(FockChunk) + partial_bytes) +
          (size_t)c.lay.nd * (sizeof(HafDigit) + 4) + (size_t)c.g.K * 8 + sizeof(HafMat) + 80;
 }
 
@@ -212,6 +213,22 @@ void haf_cpu(const HafSlab& S, int threads, double* out) {
 
 }  // namespace
 
+uint64_t haf_fill_slab(HafSlab& S, const HafIn& in, int n, uint64_t k, uint64_t kend, uint64_t slab_max,
+                       size_t partial_bytes, bool host_tables) {
+  HafProgs progs;
+  size_t bytes = 0;
+  const uint64_t k0 = k;
+  for (; k < kend && k - k0 < slab_max; ++k) {
+    const HafChoice c = haf_choose(in.idx + k * n, n);
+    const size_t add = haf_bytes(c, partial_bytes);
+    const uint64_t chunks = (c.lay.H + 63) / 64;
+    if (k > k0 && (bytes + add > kHafSlabCapBytes || S.chunks.size() + chunks > 0x7fffffffull)) break;
+    haf_append(S, in, c, progs, host_tables);
+    bytes += add;
+  }
+  return k;
+}
+
 int hafnian_plan(const int32_t* idx, int n, uint64_t count, uint64_t* terms) {
   if (!idx) {
     set_error("sup_hafnian_complex_plan: null index list");
@@ -226,13 +243,7 @@ int hafnian_plan(const int32_t* idx, int n, uint64_t count, uint64_t* terms) {
   return SUP_OK;
 }
 
-int hafnian_complex(const HafIn& in, int n, uint64_t count, const sup_opts& o, bool on_cpu, double* out,
-                    HafInfo* info) {
-  const std::string who = in.loop ? "sup_loop_hafnian_complex" : "sup_hafnian_complex";
-  if (!out || !in.A || !in.idx || (in.loop && !in.mu)) {
-    set_error(who + ": null pointer");
-    return SUP_EINVAL;
-  }
+int haf_check_request(const HafIn& in, int n, uint64_t count, const std::string& who) {
   if (n < 1 || n > SUP_MAX_N) {
     set_error("n = " + std::to_string(n) + " outside [1, 64] (64-bit Gray index)");
     return SUP_EINVAL;
@@ -257,6 +268,17 @@ int hafnian_complex(const HafIn& in, int n, uint64_t count, const sup_opts& o, b
         return SUP_EINVAL;
       }
     }
+  return SUP_OK;
+}
+
+int hafnian_complex(const HafIn& in, int n, uint64_t count, const sup_opts& o, bool on_cpu, double* out,
+                    HafInfo* info) {
+  const std::string who = in.loop ? "sup_loop_hafnian_complex" : "sup_hafnian_complex";
+  if (!out || !in.A || !in.idx || (in.loop && !in.mu)) {
+    set_error(who + ": null pointer");
+    return SUP_EINVAL;
+  }
+  if (int rc = haf_check_request(in, n, count, who)) return rc;
   HafInfo hi;
   if (info) *info = hi;
   if (count == 0) return SUP_OK;
@@ -332,17 +354,8 @@ int hafnian_complex(const HafIn& in, int n, uint64_t count, const sup_opts& o, b
         S.loop = in.loop;
         S.coef = coef;
         S.div = in.loop ? 1.0 : fact[n / 2];
-        HafProgs progs;
-        size_t bytes = 0;
         const uint64_t k0 = k;
-        for (; k < b && k - k0 < slab_max; ++k) {
-          const HafChoice c = haf_choose(in.idx + k * n, n);
-          const size_t add = haf_bytes(c);
-          const uint64_t chunks = (c.lay.H + 63) / 64;
-          if (k > k0 && (bytes + add > kHafSlabCapBytes || S.chunks.size() + chunks > 0x7fffffffull)) break;
-          haf_append(S, in, c, progs, on_cpu);
-          bytes += add;
-        }
+        k = haf_fill_slab(S, in, n, k, b, slab_max, 16, on_cpu);
         if (on_cpu) {
           haf_cpu(S, std::max(o.threads, 1), out + 2 * k0);
         } else {

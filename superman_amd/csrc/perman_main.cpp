@@ -45,6 +45,10 @@
 // --hafnian --powertrace: the same value through sup_hafnian_complex_pt /
 // sup_loop_hafnian_complex_pt (2^(n/2) subsets instead of 2^(n-1) states; on
 // the device up to n = SUP_HAFNIAN_PT_MAX_DEVICE_N, with -c up to 64).
+// --hafnian --exact [--loop] [--rpt ...]: the exact value of a file whose parts
+// are integers, through sup_hafnian_complex_exact (residue walk and CRT, -g or
+// -c, n <= 64); prints "Hafnian (exact): <re> <im>", two decimal integers.
+// Refused with --powertrace.
 // --torontonian [--modes 0,3,5]: sup_torontonian of a 2M x 2M Hermitian
 // MatrixMarket `complex` file (thewalrus' ordering) on the listed distinct
 // modes (default: all M); prints "Torontonian: <value>".  -g the device
@@ -224,7 +228,7 @@ int run_hafnian_cli(const Cli& c) {
     bool on;
     const char* opt;
   } refused[] = {{!c.dense, "-s"},       {c.compression, "-o"},    {c.scaling > 0.0, "-u"},
-                 {c.exact, "-E"},        {c.quad, "-q"},           {c.approximation, "-a"},
+                 {c.quad, "-q"},         {c.approximation, "-a"},
                  {!c.generic, "-b"},     {c.grid_graph, "-i"},     {c.preprocessing_given, "-r"},
                  {c.complex, "--complex"}, {c.complex_quad, "--complex-quad"}, {c.complex_exact, "--complex-exact"}};
   for (const auto& r : refused)
@@ -232,6 +236,10 @@ int run_hafnian_cli(const Cli& c) {
       std::fprintf(stderr, "perman: --hafnian does not combine with %s\n", r.opt);
       return 1;
     }
+  if (c.exact && c.powertrace) {  // -E / --exact beside --hafnian: the exact Kan walk
+    std::fprintf(stderr, "perman: --hafnian --exact does not combine with --powertrace\n");
+    return 1;
+  }
   double* mat = nullptr;
   int M = 0, nnz = 0;
   if (sup_read_mtx_complex(c.filename.c_str(), &mat, &M, &nnz) != SUP_OK) return fail("reading complex matrix");
@@ -265,11 +273,15 @@ int run_hafnian_cli(const Cli& c) {
   o.device_id = c.device;
   o.threads = c.threads;
   double out[2] = {0.0, 0.0};
+  char xre[768] = "0", xim[768] = "0";  // --exact: decimal integers
   sup_stats st;
   int rc = SUP_OK;
   const auto t0 = std::chrono::steady_clock::now();
   for (int rep = 0; rep < c.reps && rc == SUP_OK; ++rep)
-    if (c.powertrace)
+    if (c.exact)
+      rc = sup_hafnian_complex_exact(mat, M, c.loop ? mu.data() : nullptr, idx.data(), (int)idx.size(), 1, &o,
+                                     c.gpu ? 0 : 1, xre, xim, sizeof(xre), &st);
+    else if (c.powertrace)
       rc = c.loop ? sup_loop_hafnian_complex_pt(mat, M, mu.data(), idx.data(), (int)idx.size(), 1, &o, c.gpu ? 0 : 1, out, &st)
                   : sup_hafnian_complex_pt(mat, M, idx.data(), (int)idx.size(), 1, &o, c.gpu ? 0 : 1, out, &st);
     else
@@ -277,14 +289,17 @@ int run_hafnian_cli(const Cli& c) {
                   : sup_hafnian_complex(mat, M, idx.data(), (int)idx.size(), 1, &o, c.gpu ? 0 : 1, out, &st);
   const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / (double)c.reps;
   sup_free(mat);
-  if (rc != SUP_OK) return fail(c.loop ? "loop hafnian" : "hafnian");
+  if (rc != SUP_OK) return fail(c.exact ? (c.loop ? "exact loop hafnian" : "exact hafnian") : c.loop ? "loop hafnian" : "hafnian");
+  if (c.exact) out[0] = std::strtod(xre, nullptr), out[1] = std::strtod(xim, nullptr);
   std::cout << "Result: " << (c.gpu ? "gpu_" : "cpu_") << (c.loop ? "loop_hafnian64_complex" : "hafnian64_complex")
-            << (c.powertrace ? "_powertrace" : "") << " "
+            << (c.powertrace ? "_powertrace" : "") << (c.exact ? "_exact" : "") << " "
             << out[0] << " " << out[1] << " in " << sec << std::endl;
-  std::printf("Hafnian: %.17e %.17e\n", out[0], out[1]);
+  if (c.exact) std::printf("Hafnian (exact): %s %s\n", xre, xim);
+  else std::printf("Hafnian: %.17e %.17e\n", out[0], out[1]);
   if (c.verbose)
     std::printf("Stats: devices %d kernel_ms %.3f wall_ms %.3f terms %llu grid %d\n", st.devices_used, st.kernel_ms,
                 st.wall_ms, (unsigned long long)st.visited_steps, st.grid);
+  if (c.verbose && c.exact) std::printf("Exact: primes %d launches %d\n", (int)st.seg_cached_bits, (int)st.seg_pair_bits);
   return 0;
 }
 

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SUP_ABI_VERSION 23  /* 23: sup_hafnian_complex_exact; 22: sup_torontonian, sup_torontonian_range, sup_torontonian_plan, SUP_TORONTONIAN_MAX_DEVICE_N; 21: sup_hafnian_complex_pt, sup_loop_hafnian_complex_pt, sup_hafnian_complex_pt_range, sup_hafnian_complex_pt_plan, SUP_HAFNIAN_PT_MAX_DEVICE_N; 20: sup_hafnian_complex, sup_loop_hafnian_complex, sup_hafnian_complex_plan; 19: sup_perman_complex_exact, sup_perman_complex_exact_range, SUP_CPLX_EXACT_MAX_DEVICE_N; 18: sup_perman_complex_quad, sup_perman_complex_quad_range, SUP_CPLX_QUAD_MAX_DEVICE_N; 17:sup_perman_complex_fock_minors, sup_perman_complex_fock_minors_plan, sup_boson_sample_fock; 16: sup_plan_census; 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
+#define SUP_ABI_VERSION 24  /* 24: sup_loop_torontonian, sup_loop_torontonian_range, sup_loop_torontonian_plan, sup_ltor_exp, sup_ltor_exp_device, SUP_LOOP_TORONTONIAN_MAX_DEVICE_N; 23: sup_hafnian_complex_exact; 22: sup_torontonian, sup_torontonian_range, sup_torontonian_plan, SUP_TORONTONIAN_MAX_DEVICE_N; 21: sup_hafnian_complex_pt, sup_loop_hafnian_complex_pt, sup_hafnian_complex_pt_range, sup_hafnian_complex_pt_plan, SUP_HAFNIAN_PT_MAX_DEVICE_N; 20: sup_hafnian_complex, sup_loop_hafnian_complex, sup_hafnian_complex_plan; 19: sup_perman_complex_exact, sup_perman_complex_exact_range, SUP_CPLX_EXACT_MAX_DEVICE_N; 18: sup_perman_complex_quad, sup_perman_complex_quad_range, SUP_CPLX_QUAD_MAX_DEVICE_N; 17:sup_perman_complex_fock_minors, sup_perman_complex_fock_minors_plan, sup_boson_sample_fock; 16: sup_plan_census; 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SUP_OK            0
@@ -870,6 +870,42 @@ int sup_torontonian_range(const double* O, int M, const int32_t* modes, int n, u
  * per subset.  Host only; either output may be NULL.  n outside [1, 32]:
  * SUP_EINVAL. */
 int sup_torontonian_plan(int n, uint64_t* subsets, double* est_ops);
+
+/* Loop torontonians (ABI 24): click patterns of DISPLACED Gaussian states on
+ * threshold detectors (thewalrus' ltor).  O, M, modes, n and z are the
+ * torontonian's; gamma is any complex vector of length 2M (interleaved pairs;
+ * entry i: mode i, entry i + M: its partner), gathered with the same rows:
+ *   ltor(O, gamma, s) = sum_z (-1)^(n - |z|) f(z),
+ *   f(z) = exp(1/2 gamma_z^H (I - O_z)^-1 gamma_z) / sqrt det(I - O_z),  f(0) = 1
+ * The quadratic form is the diagonal chain of one more row of the
+ * torontonian's factor, and the exponential is built from fma, multiply, rint
+ * and exponent-field arithmetic only (superman_amd/csrc/ltor.hpp, DESIGN.md
+ * 8l): out[k] is a function of (O, gamma, modes[k]) only, bit-identical on the
+ * device (walk_ltor.hip), on any device count, for any queue group and on host
+ * threads (on_cpu = 1).  gamma = 0 gives sup_torontonian's bits.  A pivot that
+ * is not positive gives NaN, an exponent beyond the fp64 range inf or NaN:
+ * neither is an error code.
+ * Errors and st as sup_torontonian's, with a null gamma among the null
+ * pointers; the cap is SUP_LOOP_TORONTONIAN_MAX_DEVICE_N; est_ops_per_step =
+ * the census ltor_ops(n). */
+#define SUP_LOOP_TORONTONIAN_MAX_DEVICE_N 32
+int sup_loop_torontonian(const double* O, int M, const double* gamma, const int32_t* modes, int n, uint64_t count,
+                         const sup_opts* o, int on_cpu, double* out, sup_stats* st);
+/* One list, the subsets z in [z_begin, z_end) only: sup_torontonian_range's
+ * chunks, folds and rules. */
+int sup_loop_torontonian_range(const double* O, int M, const double* gamma, const int32_t* modes, int n,
+                               uint64_t z_begin, uint64_t z_end, const sup_opts* o, int on_cpu, double* out,
+                               sup_stats* st);
+/* The subsets one list of n modes visits (2^n) and the census' fp64 operations
+ * per subset.  Host only; either output may be NULL.  n outside [1, 32]:
+ * SUP_EINVAL. */
+int sup_loop_torontonian_plan(int n, uint64_t* subsets, double* est_ops);
+/* The exponential of the loop torontonian's terms (ltor.hpp ltor_exp), exported
+ * for the test harness: on the host, and elementwise on device device_id
+ * (out[i] = ltor_exp(x[i]); a null pointer: SUP_EINVAL, no device: SUP_ENODEV;
+ * count = 0 does nothing).  The two agree bit for bit. */
+double sup_ltor_exp(double x);
+int sup_ltor_exp_device(const double* x, uint64_t count, double* out, int device_id);
 
 /* Nijenhuis-Wilf prologue (gpu_exact_dense.cu:642-652): x0[j] = a[j][n-1] - rowsum_j/2,
  * p0 = prod x0.  Host-only helper, exported for the test harness. */

@@ -26,6 +26,8 @@ __all__ = [
            "hafnian_powertrace", "loop_hafnian_powertrace", "hafnian_powertrace_batch", "hafnian_powertrace_range",
            "hafnian_powertrace_plan", "HAFNIAN_PT_MAX_DEVICE_N",
            "torontonian", "torontonian_batch", "torontonian_range", "torontonian_plan", "TORONTONIAN_MAX_DEVICE_N",
+           "loop_torontonian", "loop_torontonian_batch", "loop_torontonian_range", "loop_torontonian_plan",
+           "LOOP_TORONTONIAN_MAX_DEVICE_N", "ltor_exp", "threshold_detection_prob", "threshold_detection_probs",
            "perman_complex_fock_minors_plan","perman_complex_minors", "perman_complex_minors_submatrices", "perman_complex_minors_range", "boson_sample", "read_mtx_complex", "partial", "perman_shard", "plan_info", "plan_census", "CENSUS_CLASSES", "plan_key", "prepare", "read_matrix", "read_mtx", "sort_order",
     "skip_order", "compress", "decompose", "perman_reduced", "approx", "grid_graph", "ALGOS_APPROX",
     "nw_start", "device_count", "rccl_devices", "layout", "ShardCall", "SupError", "ALGOS_DENSE", "ALGOS_SPARSE",
@@ -1041,6 +1043,157 @@ def torontonian_plan(n: int):
     subsets, ops = C.c_uint64(0), C.c_double(0.0)
     _lib.check(_lib.load().sup_torontonian_plan(int(n), C.byref(subsets), C.byref(ops)), "torontonian_plan")
     return int(subsets.value), float(ops.value)
+
+
+# include/superman.h SUP_LOOP_TORONTONIAN_MAX_DEVICE_N: the largest number of
+# modes the loop torontonian kernel serves on the device (every n the entry takes)
+LOOP_TORONTONIAN_MAX_DEVICE_N = 32
+
+
+def _ltor_gamma(gamma, o):
+    g = np.asarray(gamma, dtype=np.complex128)
+    if g.ndim == 0:
+        g = np.full(o.shape[0], complex(g), dtype=np.complex128)
+    g = np.ascontiguousarray(g)
+    if g.shape != (o.shape[0],):
+        raise ValueError(f"gamma must have the 2M = {o.shape[0]} entries of O's rows, got shape {g.shape}")
+    return g
+
+
+def loop_torontonian_batch(O, gamma, modes, gpu_num: int = 1, device_id: int = 0, cpu: bool = False, threads: int = 16,
+                           return_stats: bool = False):
+    """The loop torontonians (thewalrus' ``ltor``) of the 2M x 2M Hermitian
+    matrix ``O`` and the complex vector ``gamma`` of length 2M (a scalar fills
+    it) on lists of distinct modes (sup_loop_torontonian): O and gamma in
+    thewalrus' ordering, ``modes`` of shape [n] (a float) or [count, n] (an
+    array).  The kernel walk_ltor.hip or (cpu=True) its host twin,
+    bit-identical; gamma = 0 has ``torontonian_batch``'s bits."""
+    o = _tor_matrix(O)
+    g = _ltor_gamma(gamma, o)
+    i32, count, n, single = _tor_lists(modes)
+    lib = _lib.load()
+    op = _opts(gpu_num=gpu_num, device_id=device_id, threads=threads)
+    out, st = np.zeros(max(count, 1)), SupStats()
+    rc = lib.sup_loop_torontonian(o.ctypes.data, o.shape[0] // 2, g.ctypes.data, i32.ctypes.data, n, count, C.byref(op),
+                                  int(bool(cpu)), out.ctypes.data, C.byref(st))
+    _lib.check(rc, "loop_torontonian")
+    v = float(out[0]) if single else out[:count].copy()
+    return (v, st.as_dict()) if return_stats else v
+
+
+def loop_torontonian(O, gamma, **kw):
+    """The loop torontonian of the whole matrix O and vector gamma
+    (``loop_torontonian_batch`` with modes = 0..M-1), as thewalrus' ``ltor``."""
+    return loop_torontonian_batch(O, gamma, np.arange(np.shape(O)[0] // 2), **kw)
+
+
+def loop_torontonian_range(O, gamma, modes, z_begin: int, z_end: int, device_id: int = 0, cpu: bool = False,
+                           threads: int = 16, return_stats: bool = False):
+    """The part of one list's loop torontonian sum from the subsets z in
+    [z_begin, z_end) (sup_loop_torontonian_range), cut and folded as
+    ``torontonian_range``."""
+    o = _tor_matrix(O)
+    g = _ltor_gamma(gamma, o)
+    i32, count, n, single = _tor_lists(modes)
+    if not single:
+        raise ValueError("loop_torontonian_range takes one list of modes of shape [n]")
+    if not (0 <= int(z_begin) < 2**64 and 0 <= int(z_end) < 2**64):
+        raise ValueError("z_begin and z_end must be unsigned 64-bit integers")
+    lib = _lib.load()
+    op = _opts(gpu_num=1, device_id=device_id, threads=threads)
+    out, st = np.zeros(1), SupStats()
+    rc = lib.sup_loop_torontonian_range(o.ctypes.data, o.shape[0] // 2, g.ctypes.data, i32.ctypes.data, n, int(z_begin),
+                                        int(z_end), C.byref(op), int(bool(cpu)), out.ctypes.data, C.byref(st))
+    _lib.check(rc, "loop_torontonian_range")
+    v = float(out[0])
+    return (v, st.as_dict()) if return_stats else v
+
+
+def loop_torontonian_plan(n: int):
+    """(subsets, fp64 operations per subset) of one list of n modes
+    (sup_loop_torontonian_plan, host only)."""
+    subsets, ops = C.c_uint64(0), C.c_double(0.0)
+    _lib.check(_lib.load().sup_loop_torontonian_plan(int(n), C.byref(subsets), C.byref(ops)), "loop_torontonian_plan")
+    return int(subsets.value), float(ops.value)
+
+
+def ltor_exp(x, device: bool = False, device_id: int = 0):
+    """The exponential of the loop torontonian's terms (ltor.hpp ltor_exp:
+    fma, multiply, rint and exponent-field arithmetic only), on the host or
+    elementwise on the device; the two agree bit for bit.  A scalar gives a
+    float, an array an array."""
+    a = np.asarray(x, dtype=np.float64)
+    lib = _lib.load()
+    flat = np.ascontiguousarray(a.reshape(-1))
+    out = np.zeros(flat.shape[0])
+    if device:
+        _lib.check(lib.sup_ltor_exp_device(flat.ctypes.data, flat.shape[0], out.ctypes.data, int(device_id)), "ltor_exp")
+    else:
+        for i in range(flat.shape[0]):
+            out[i] = lib.sup_ltor_exp(float(flat[i]))
+    return float(out[0]) if a.ndim == 0 else out.reshape(a.shape)
+
+
+def _threshold_setup(mu, cov, hbar):
+    """(O, gamma or None, prefactor) of a Gaussian state in xxpp ordering:
+    W = [[I, iI], [I, -iI]] / sqrt 2, sigma = W cov W^H / hbar, Q = sigma + I / 2,
+    alpha = W mu / sqrt hbar, O = I - Q^-1, gamma = Q^-1 alpha, prefactor =
+    exp(-1/2 alpha^H Q^-1 alpha) / sqrt det Q."""
+    cov = np.asarray(cov, dtype=np.float64)
+    if cov.ndim != 2 or cov.shape[0] != cov.shape[1] or cov.shape[0] < 2 or cov.shape[0] % 2:
+        raise ValueError(f"expected a 2M x 2M covariance matrix with M >= 1, got shape {cov.shape}")
+    M = cov.shape[0] // 2
+    I = np.eye(M)
+    W = np.block([[I, 1j * I], [I, -1j * I]]) / np.sqrt(2.0)
+    Q = W @ cov @ W.conj().T / float(hbar) + np.eye(2 * M) / 2.0
+    Qi = np.linalg.inv(Q)
+    Qi = (Qi + Qi.conj().T) / 2.0
+    O = np.eye(2 * M) - Qi
+    pre = 1.0 / np.sqrt(np.linalg.det(Q).real)
+    if mu is None:
+        return O, None, float(pre)
+    mu = np.asarray(mu, dtype=np.float64)
+    if mu.shape != (2 * M,):
+        raise ValueError(f"mu must have the 2M = {2 * M} entries of cov's rows, got shape {mu.shape}")
+    alpha = W @ mu / np.sqrt(float(hbar))
+    gamma = Qi @ alpha
+    return O, gamma, float(pre * np.exp(-0.5 * (alpha.conj() @ gamma).real))
+
+
+def threshold_detection_probs(mu, cov, patterns, hbar: float = 2.0, **kw):
+    """The probabilities of click patterns (shape [count, M] of 0 / 1, or one
+    pattern of shape [M]) of the Gaussian state with mean ``mu`` and covariance
+    ``cov`` (xxpp ordering, vacuum = hbar / 2) on threshold detectors: the
+    prefactor times the loop torontonian on the clicked modes, one batched
+    ``loop_torontonian_batch`` call per click count (numpy does the setup on
+    the host).  ``mu=None``: no displacement, through ``torontonian_batch``
+    and with its bits.  ``kw`` goes to the batch call (cpu, threads, gpu_num,
+    device_id)."""
+    O, gamma, pre = _threshold_setup(mu, cov, hbar)
+    M = O.shape[0] // 2
+    pat = np.asarray(patterns)
+    single = pat.ndim == 1
+    if single:
+        pat = pat[None, :]
+    if pat.ndim != 2 or pat.shape[1] != M or not np.all((pat == 0) | (pat == 1)):
+        raise ValueError(f"patterns must be 0 / 1 with shape [M] or [count, M], M = {M}; got shape {np.shape(patterns)}")
+    pat = pat.astype(bool)
+    clicks = pat.sum(1)
+    out = np.zeros(pat.shape[0])
+    for k in np.unique(clicks):
+        which = np.nonzero(clicks == k)[0]
+        if k == 0:
+            out[which] = pre  # the empty pattern: the prefactor alone
+            continue
+        modes = np.stack([np.nonzero(pat[i])[0] for i in which]).astype(np.int32)
+        v = torontonian_batch(O, modes, **kw) if gamma is None else loop_torontonian_batch(O, gamma, modes, **kw)
+        out[which] = pre * np.asarray(v)
+    return float(out[0]) if single else out
+
+
+def threshold_detection_prob(mu, cov, clicks, hbar: float = 2.0, **kw):
+    """The probability of one click pattern (``threshold_detection_probs``)."""
+    return threshold_detection_probs(mu, cov, np.asarray(clicks).reshape(-1), hbar=hbar, **kw)
 
 
 def partial(mat, start: int, end: int, kernel: str = "dense", gpu_num: int = 1, device_id: int = 0,

@@ -46,6 +46,7 @@ EXPORTS = [
     "sup_hafnian_complex", "sup_loop_hafnian_complex", "sup_hafnian_complex_plan", "sup_hafnian_complex_exact",
     "sup_hafnian_complex_pt", "sup_loop_hafnian_complex_pt", "sup_hafnian_complex_pt_range", "sup_hafnian_complex_pt_plan",
     "sup_torontonian", "sup_torontonian_range", "sup_torontonian_plan",
+    "sup_loop_torontonian", "sup_loop_torontonian_range", "sup_loop_torontonian_plan", "sup_ltor_exp", "sup_ltor_exp_device",
     "sup_gpu_perman64_xshared_coalescing_mshared",
     "sup_gpu_perman64_xshared_coalescing_mshared_multigpu",
     "sup_gpu_perman64_xshared_coalescing_mshared_multigpucpu_chunks",
@@ -140,7 +141,7 @@ def load() -> C.CDLL:
             build()
         lib = C.CDLL(LIB_PATH)
         _declare(lib)
-        if lib.sup_abi_version() != 23:
+        if lib.sup_abi_version() != 24:
             raise RuntimeError("libsuperman_hip.so ABI version mismatch")
         _lib = lib
         return lib
@@ -209,6 +210,13 @@ def _declare(lib: C.CDLL) -> None:
     lib.sup_torontonian_range.argtypes = [P, I, P, I, C.c_uint64, C.c_uint64, C.POINTER(SupOpts), I, P,
                                           C.POINTER(SupStats)]
     lib.sup_torontonian_plan.argtypes = [I, C.POINTER(C.c_uint64), C.POINTER(D)]
+    lib.sup_loop_torontonian.argtypes = [P, I, P, P, I, C.c_uint64, C.POINTER(SupOpts), I, P, C.POINTER(SupStats)]
+    lib.sup_loop_torontonian_range.argtypes = [P, I, P, P, I, C.c_uint64, C.c_uint64, C.POINTER(SupOpts), I, P,
+                                               C.POINTER(SupStats)]
+    lib.sup_loop_torontonian_plan.argtypes = [I, C.POINTER(C.c_uint64), C.POINTER(D)]
+    lib.sup_ltor_exp.argtypes = [D]
+    lib.sup_ltor_exp.restype = D
+    lib.sup_ltor_exp_device.argtypes = [P, C.c_uint64, P, I]
     lib.sup_read_mtx_complex.argtypes = [C.c_char_p, C.POINTER(P), C.POINTER(I), C.POINTER(I)]
     lib.sup_perman_shard.argtypes = [P, I, I, I, I, I, C.POINTER(SupOpts), C.POINTER(D), C.POINTER(SupStats)]
     lib.sup_plan_info.argtypes = [P, I, I, I, C.POINTER(SupOpts), C.POINTER(I), P, C.POINTER(I), C.POINTER(I),
@@ -238,7 +246,7 @@ def _declare(lib: C.CDLL) -> None:
     lib.sup_perman_reduced.argtypes = [P, I, I, I, I, C.POINTER(SupOpts), I, C.POINTER(SupReduceOpts),
                                        C.POINTER(D), C.POINTER(SupStats)]
     for name in EXPORTS:
-        if name not in ("sup_opts_init", "sup_free", "sup_last_error", "sup_reduce_opts_init"):
+        if name not in ("sup_opts_init", "sup_free", "sup_last_error", "sup_reduce_opts_init", "sup_ltor_exp"):
             getattr(lib, name).restype = I
 
 

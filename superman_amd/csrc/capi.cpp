@@ -9,6 +9,7 @@
 #include "engine.hpp"
 #include "hafnian_exact.hpp"
 #include "hafnian_pt.hpp"
+#include "loop_torontonian.hpp"
 #include "torontonian.hpp"
 
 using namespace sup;
@@ -790,6 +791,70 @@ int sup_torontonian_range(const double* O, int M, const int32_t* modes, int n, u
 }
 
 int sup_torontonian_plan(int n, uint64_t* subsets, double* est_ops) { return torontonian_plan(n, subsets, est_ops); }
+
+static int loop_torontonian_entry(const LtorIn& in, int n, uint64_t count, bool range, uint64_t z0, uint64_t z1,
+                                  const sup_opts* o_in, int on_cpu, double* out, sup_stats* st) {
+  auto t0 = std::chrono::steady_clock::now();
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  if (range) o.gpu_num = 1;
+  TorInfo ti;
+  if (int rc = loop_torontonian(in, n, count, range, z0, z1, o, on_cpu != 0, out, &ti)) return rc;
+  if (st) {
+    std::memset(st, 0, sizeof(*st));
+    st->kernel_ms = ti.kernel_ms;
+    st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    st->gray_steps = count << n;
+    st->visited_steps = ti.subsets;
+    st->devices_used = ti.devices;
+    st->grid = ti.grid;
+    st->walk_kind = (int)kWalkDense;
+    st->leaves = (int)std::min<uint64_t>(count, 0x7fffffffu);
+    st->est_ops_per_step = ti.ops;
+  }
+  return SUP_OK;
+}
+
+int sup_loop_torontonian(const double* O, int M, const double* gamma, const int32_t* modes, int n, uint64_t count,
+                         const sup_opts* o, int on_cpu, double* out, sup_stats* st) {
+  LtorIn in;
+  in.O = O, in.M = M, in.gamma = gamma, in.modes = modes;
+  return loop_torontonian_entry(in, n, count, false, 0, 0, o, on_cpu, out, st);
+}
+
+int sup_loop_torontonian_range(const double* O, int M, const double* gamma, const int32_t* modes, int n,
+                               uint64_t z_begin, uint64_t z_end, const sup_opts* o, int on_cpu, double* out,
+                               sup_stats* st) {
+  LtorIn in;
+  in.O = O, in.M = M, in.gamma = gamma, in.modes = modes;
+  return loop_torontonian_entry(in, n, 1, true, z_begin, z_end, o, on_cpu, out, st);
+}
+
+int sup_loop_torontonian_plan(int n, uint64_t* subsets, double* est_ops) {
+  return loop_torontonian_plan(n, subsets, est_ops);
+}
+
+double sup_ltor_exp(double x) { return ltor_exp(x); }
+
+int sup_ltor_exp_device(const double* x, uint64_t count, double* out, int device_id) {
+  if (count == 0) return SUP_OK;
+  if (!x || !out) {
+    set_error("sup_ltor_exp_device: null pointer");
+    return SUP_EINVAL;
+  }
+  int ndev = 0;
+  if (int rc = device_count(&ndev)) return rc;
+  if (ndev == 0) {
+    set_error("no HIP device available (sup_ltor_exp_device; sup_ltor_exp is the host's)");
+    return SUP_ENODEV;
+  }
+  if (device_id < 0 || device_id >= ndev) {
+    set_error("sup_ltor_exp_device: device_id out of range");
+    return SUP_EINVAL;
+  }
+  return run_ltor_exp(device_id, x, count, out);
+}
 
 // sup_stats of a minors call: the batch entry's, with the one-walk step cost.
 static void fill_minors_stats(sup_stats* st, const CplxInfo& ci, int n, uint64_t outputs, uint64_t steps,

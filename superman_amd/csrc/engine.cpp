@@ -5,6 +5,7 @@
 #include "engine.hpp"
 #include "hafnian_exact.hpp"
 #include "hafnian_pt.hpp"
+#include "loop_torontonian.hpp"
 #include "torontonian.hpp"
 
 #include <hip/hip_runtime.h>
@@ -1736,6 +1737,97 @@ int run_torontonian(int dev, const TorIn& in, int n, uint64_t first, uint64_t K,
   SUP_HIP(hipMemcpyAsync(out, c->d_cbout, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, s));
   if (grid_out) *grid_out = (int)geo.grid;
   return timed_sync(c, kernel_ms);
+}
+
+// Loop torontonian kernel (walk_ltor.hip), as run_torontonian: O, gamma (behind
+// O in the same buffer) and the lists go up once, prepare gathers the matrices
+// and border rows on the device, then the walk and the torontonian's fold.
+int run_loop_torontonian(int dev, const LtorIn& in, int n, uint64_t first, uint64_t K, uint64_t z_begin, uint64_t z_end,
+                         double* out, double* kernel_ms, int* grid_out) {
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (grid_out) *grid_out = 0;
+  if (K == 0) return SUP_OK;
+  if (n < 1 || n > SUP_LOOP_TORONTONIAN_MAX_DEVICE_N || ltor_lds_bytes(n) > 65536 || !out || !in.O || !in.gamma ||
+      !in.modes || in.M < 1 || z_begin >= z_end || z_end > (1ull << n)) {
+    set_error("run_loop_torontonian: bad request");
+    return SUP_EINVAL;
+  }
+  const int llog = tor_chunk_log(n);
+  const uint64_t cfirst = z_begin >> llog, cm = ((z_end + (1ull << llog) - 1) >> llog) - cfirst;
+  const uint64_t chunks = K * cm, g_doubles = ltor_g_doubles(n);
+  if (cm > 0xffffffffull || chunks > 0x7fffffffull) {
+    set_error("run_loop_torontonian: too many wave-chunks in one slab");
+    return SUP_EINVAL;
+  }
+  const size_t o_doubles = (size_t)8 * in.M * in.M, gm_doubles = (size_t)4 * in.M;
+  CtxGuard guard;
+  int rc = guard.open(dev, "device buffers");
+  if (rc) return rc;
+  DeviceCtx* c = guard.c;
+  int occ = 0;
+  SUP_HIP(ltor_occupancy(n, &occ));
+  if ((rc = ensure(c->d_cbtab, c->cbtab_cap, (size_t)(K * g_doubles)))) return rc;
+  if ((rc = ensure(c->d_cbidx, c->cbidx_cap, (size_t)K * n))) return rc;
+  if ((rc = ensure(c->d_cbU, c->cbU_cap, o_doubles + gm_doubles))) return rc;
+  if ((rc = ensure(c->d_chunk, c->chunk_cap, (size_t)(2 * chunks)))) return rc;
+  if ((rc = ensure(c->d_cbout, c->cbout_cap, (size_t)K))) return rc;
+  hipStream_t s = c->stream;
+  c->tables_uid = 0;  // the walk leaves head 0 nonzero
+  c->head_zero[0] = false;
+  SUP_HIP(hipMemcpyAsync(c->d_cbU, in.O, o_doubles * sizeof(double), hipMemcpyHostToDevice, s));
+  SUP_HIP(hipMemcpyAsync(c->d_cbU + o_doubles, in.gamma, gm_doubles * sizeof(double), hipMemcpyHostToDevice, s));
+  SUP_HIP(hipMemcpyAsync(c->d_cbidx, in.modes + first * n, (size_t)K * n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  SUP_HIP(hipMemsetAsync(c->d_counter, 0, sizeof(unsigned), s));
+  const uint64_t resident = (uint64_t)c->cus * (uint64_t)std::max(occ, 1);
+  const char* fg = std::getenv("SUP_WALK_GROUP");  // tests, read per call: chunks per ticket (the bits do not change)
+  const LaunchGeom geo = walk_geometry(chunks, resident, 1, false, fg ? std::max(1, std::atoi(fg)) : 0);
+  TorParams p{};
+  p.G = c->d_cbtab;
+  p.chunk_count = chunks;
+  p.chunk_out = c->d_chunk;
+  p.counter = c->d_counter;
+  p.group = geo.group;
+  p.n = (unsigned)n;
+  p.nn = (unsigned)tor_nn(n);
+  p.llog = (unsigned)llog;
+  p.cm = (unsigned)cm;
+  p.z_begin = z_begin;
+  p.z_end = z_end;
+  p.chunk_first = cfirst;
+  SUP_HIP(hipEventRecord(c->ev0, s));
+  SUP_ON_DEVICE(c->dev, "loop torontonian launch");
+  SUP_HIP(launch_ltor_prepare(c->d_cbU, in.M, c->d_cbU + o_doubles, c->d_cbidx, n, K, c->d_cbtab, s));
+  SUP_HIP(launch_ltor(p, (int)geo.grid, s));
+  SUP_HIP(launch_tor_fold(c->d_chunk, (uint32_t)cm, K, c->d_cbout, s));
+  SUP_HIP(hipEventRecord(c->ev1, s));
+  SUP_HIP(hipMemcpyAsync(out, c->d_cbout, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (grid_out) *grid_out = (int)geo.grid;
+  return timed_sync(c, kernel_ms);
+}
+
+// out[i] = ltor_exp(x[i]) on the device (sup_ltor_exp_device), in the
+// collision-aware walk's buffers.
+int run_ltor_exp(int dev, const double* x, uint64_t count, double* out) {
+  if (count == 0) return SUP_OK;
+  if (!x || !out) {
+    set_error("run_ltor_exp: null pointer");
+    return SUP_EINVAL;
+  }
+  CtxGuard guard;
+  int rc = guard.open(dev, "device buffers");
+  if (rc) return rc;
+  DeviceCtx* c = guard.c;
+  if ((rc = ensure(c->d_cbtab, c->cbtab_cap, (size_t)count))) return rc;
+  if ((rc = ensure(c->d_cbout, c->cbout_cap, (size_t)count))) return rc;
+  hipStream_t s = c->stream;
+  SUP_HIP(hipMemcpyAsync(c->d_cbtab, x, (size_t)count * sizeof(double), hipMemcpyHostToDevice, s));
+  SUP_HIP(hipEventRecord(c->ev0, s));
+  SUP_ON_DEVICE(c->dev, "ltor_exp launch");
+  SUP_HIP(launch_ltor_exp(c->d_cbtab, count, c->d_cbout, s));
+  SUP_HIP(hipEventRecord(c->ev1, s));
+  SUP_HIP(hipMemcpyAsync(out, c->d_cbout, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, s));
+  double ms = 0.0;
+  return timed_sync(c, &ms);
 }
 
 }  // namespace sup

@@ -53,13 +53,19 @@
 // MatrixMarket `complex` file (thewalrus' ordering) on the listed distinct
 // modes (default: all M); prints "Torontonian: <value>".  -g the device
 // kernel, -c the host threads.
+// --torontonian --loop --gamma g.mtx [--modes ...]: sup_loop_torontonian of the
+// same file and the complex 2M x 1 MatrixMarket file g.mtx (coordinate or
+// array); prints "Loop torontonian: <value>".  --loop without --gamma, or
+// --gamma without --torontonian --loop, is an error.
 #include <getopt.h>
 
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <iostream>
+#include <sstream>
 #include <string>
 #include <thread>
 #include <vector>
@@ -80,7 +86,7 @@ struct Cli {
   unsigned long long seed = 1;
   int jit = 0;
   std::string filename, checkpoint, rpt;
-  std::string modes;
+  std::string modes, gamma;
 };
 
 int fail(const char* what) {
@@ -303,8 +309,43 @@ int run_hafnian_cli(const Cli& c) {
   return 0;
 }
 
+// --gamma: a complex N x 1 MatrixMarket file, coordinate ("i 1 re im" lines; the
+// entries not named are zero) or array ("re im" lines), into N interleaved pairs.
+bool read_gamma(const std::string& path, int N, std::vector<double>& g) {
+  std::ifstream in(path);
+  std::string line, tag, object, format, field;
+  if (!in || !std::getline(in, line)) {
+    std::fprintf(stderr, "perman: cannot read the --gamma file %s\n", path.c_str());
+    return false;
+  }
+  std::istringstream ban(line);
+  ban >> tag >> object >> format >> field;
+  if (tag != "%%MatrixMarket" || object != "matrix" || (format != "coordinate" && format != "array") || field != "complex") {
+    std::fprintf(stderr, "perman: --gamma takes a MatrixMarket 'matrix coordinate complex' or 'matrix array complex' file\n");
+    return false;
+  }
+  while (in.peek() == '%') std::getline(in, line);
+  long rows = 0, cols = 0, nz = 0;
+  const bool coord = format == "coordinate";
+  if (!(in >> rows >> cols) || (coord && !(in >> nz)) || rows != N || cols != 1 || nz < 0) {
+    std::fprintf(stderr, "perman: --gamma needs a %d x 1 vector, the order of the matrix\n", N);
+    return false;
+  }
+  g.assign((size_t)2 * N, 0.0);
+  for (long e = 0; e < (coord ? nz : (long)N); ++e) {
+    long i = e + 1, j = 1;
+    double re, im;
+    if ((coord && !(in >> i >> j)) || !(in >> re >> im) || i < 1 || i > N || j != 1) {
+      std::fprintf(stderr, "perman: the --gamma file's entry %ld cannot be read or lies outside the %d x 1 vector\n", e + 1, N);
+      return false;
+    }
+    g[2 * (size_t)(i - 1)] = re, g[2 * (size_t)(i - 1) + 1] = im;
+  }
+  return true;
+}
+
 // --torontonian: sup_torontonian of a Hermitian MatrixMarket `complex` file of
-// even order; the line shape follows --hafnian.
+// even order (--loop --gamma: sup_loop_torontonian); the line shape follows --hafnian.
 int run_torontonian_cli(const Cli& c) {
   const struct {
     bool on;
@@ -313,12 +354,20 @@ int run_torontonian_cli(const Cli& c) {
                  {c.exact, "-E"},        {c.quad, "-q"},           {c.approximation, "-a"},
                  {!c.generic, "-b"},     {c.grid_graph, "-i"},     {c.preprocessing_given, "-r"},
                  {c.complex, "--complex"}, {c.complex_quad, "--complex-quad"}, {c.complex_exact, "--complex-exact"},
-                 {c.hafnian, "--hafnian"}, {c.loop, "--loop"}, {!c.rpt.empty(), "--rpt"}, {c.powertrace, "--powertrace"}};
+                 {c.hafnian, "--hafnian"}, {!c.rpt.empty(), "--rpt"}, {c.powertrace, "--powertrace"}};
   for (const auto& r : refused)
     if (r.on) {
       std::fprintf(stderr, "perman: --torontonian does not combine with %s\n", r.opt);
       return 1;
     }
+  if (c.loop && c.gamma.empty()) {
+    std::fprintf(stderr, "perman: --torontonian --loop needs --gamma <file> (a complex 2M x 1 MatrixMarket file)\n");
+    return 1;
+  }
+  if (!c.loop && !c.gamma.empty()) {
+    std::fprintf(stderr, "perman: --gamma goes with --torontonian --loop\n");
+    return 1;
+  }
   double* mat = nullptr;
   int N = 0, nnz = 0;
   if (sup_read_mtx_complex(c.filename.c_str(), &mat, &N, &nnz) != SUP_OK) return fail("reading complex matrix");
@@ -349,6 +398,11 @@ int run_torontonian_cli(const Cli& c) {
     sup_free(mat);
     return 1;
   }
+  std::vector<double> gamma;
+  if (c.loop && !read_gamma(c.gamma, N, gamma)) {
+    sup_free(mat);
+    return 1;
+  }
   sup_opts o;
   sup_opts_init(&o);
   o.gpu_num = 1;
@@ -359,12 +413,14 @@ int run_torontonian_cli(const Cli& c) {
   int rc = SUP_OK;
   const auto t0 = std::chrono::steady_clock::now();
   for (int rep = 0; rep < c.reps && rc == SUP_OK; ++rep)
-    rc = sup_torontonian(mat, M, modes.data(), (int)modes.size(), 1, &o, c.gpu ? 0 : 1, &out, &st);
+    rc = c.loop ? sup_loop_torontonian(mat, M, gamma.data(), modes.data(), (int)modes.size(), 1, &o, c.gpu ? 0 : 1, &out, &st)
+                : sup_torontonian(mat, M, modes.data(), (int)modes.size(), 1, &o, c.gpu ? 0 : 1, &out, &st);
   const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / (double)c.reps;
   sup_free(mat);
-  if (rc != SUP_OK) return fail("torontonian");
-  std::cout << "Result: " << (c.gpu ? "gpu_" : "cpu_") << "torontonian64 " << out << " in " << sec << std::endl;
-  std::printf("Torontonian: %.17e\n", out);
+  if (rc != SUP_OK) return fail(c.loop ? "loop torontonian" : "torontonian");
+  std::cout << "Result: " << (c.gpu ? "gpu_" : "cpu_") << (c.loop ? "loop_torontonian64 " : "torontonian64 ") << out << " in "
+            << sec << std::endl;
+  std::printf(c.loop ? "Loop torontonian: %.17e\n" : "Torontonian: %.17e\n", out);
   if (c.verbose)
     std::printf("Stats: devices %d kernel_ms %.3f wall_ms %.3f subsets %llu grid %d\n", st.devices_used, st.kernel_ms,
                 st.wall_ms, (unsigned long long)st.visited_steps, st.grid);
@@ -400,6 +456,7 @@ int main(int argc, char** argv) {
                                         {"powertrace", 0, NULL, 1006},
                                         {"torontonian", 0, NULL, 1007},
                                         {"modes", 1, NULL, 1008},
+                                        {"gamma", 1, NULL, 1009},
                                         {NULL, 0, NULL, 0}};
   int opt;
   auto need_arg = [&](char o) -> bool {
@@ -444,6 +501,7 @@ int main(int argc, char** argv) {
       case 1006: c.powertrace = true; break;
       case 1007: c.torontonian = true; break;
       case 1008: c.modes = optarg; break;
+      case 1009: c.gamma = optarg; break;
       case 'v': c.verbose = true; break;
       // v2 flags (revised_perman/main.cpp:1431-1460): -w stores the matrix in
       // single precision (the permanent of the float-rounded entries); -h asks
@@ -474,6 +532,10 @@ int main(int argc, char** argv) {
   if (c.torontonian) return run_torontonian_cli(c);
   if (!c.modes.empty()) {
     std::fprintf(stderr, "perman: --modes goes with --torontonian\n");
+    return 1;
+  }
+  if (!c.gamma.empty()) {
+    std::fprintf(stderr, "perman: --gamma goes with --torontonian --loop\n");
     return 1;
   }
   if (c.hafnian) return run_hafnian_cli(c);

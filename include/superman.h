@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SUP_ABI_VERSION 24  /* 24: sup_loop_torontonian, sup_loop_torontonian_range, sup_loop_torontonian_plan, sup_ltor_exp, sup_ltor_exp_device, SUP_LOOP_TORONTONIAN_MAX_DEVICE_N; 23: sup_hafnian_complex_exact; 22: sup_torontonian, sup_torontonian_range, sup_torontonian_plan, SUP_TORONTONIAN_MAX_DEVICE_N; 21: sup_hafnian_complex_pt, sup_loop_hafnian_complex_pt, sup_hafnian_complex_pt_range, sup_hafnian_complex_pt_plan, SUP_HAFNIAN_PT_MAX_DEVICE_N; 20: sup_hafnian_complex, sup_loop_hafnian_complex, sup_hafnian_complex_plan; 19: sup_perman_complex_exact, sup_perman_complex_exact_range, SUP_CPLX_EXACT_MAX_DEVICE_N; 18: sup_perman_complex_quad, sup_perman_complex_quad_range, SUP_CPLX_QUAD_MAX_DEVICE_N; 17:sup_perman_complex_fock_minors, sup_perman_complex_fock_minors_plan, sup_boson_sample_fock; 16: sup_plan_census; 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
+#define SUP_ABI_VERSION 25  /* 25: sup_torontonian_table, sup_loop_torontonian_table, sup_mobius_subsets, SUP_TORONTONIAN_TABLE_MAX_N; 24: sup_loop_torontonian, sup_loop_torontonian_range, sup_loop_torontonian_plan, sup_ltor_exp, sup_ltor_exp_device, SUP_LOOP_TORONTONIAN_MAX_DEVICE_N; 23: sup_hafnian_complex_exact; 22: sup_torontonian, sup_torontonian_range, sup_torontonian_plan, SUP_TORONTONIAN_MAX_DEVICE_N; 21: sup_hafnian_complex_pt, sup_loop_hafnian_complex_pt, sup_hafnian_complex_pt_range, sup_hafnian_complex_pt_plan, SUP_HAFNIAN_PT_MAX_DEVICE_N; 20: sup_hafnian_complex, sup_loop_hafnian_complex, sup_hafnian_complex_plan; 19: sup_perman_complex_exact, sup_perman_complex_exact_range, SUP_CPLX_EXACT_MAX_DEVICE_N; 18: sup_perman_complex_quad, sup_perman_complex_quad_range, SUP_CPLX_QUAD_MAX_DEVICE_N; 17:sup_perman_complex_fock_minors, sup_perman_complex_fock_minors_plan, sup_boson_sample_fock; 16: sup_plan_census; 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SUP_OK            0
@@ -906,6 +906,40 @@ int sup_loop_torontonian_plan(int n, uint64_t* subsets, double* est_ops);
  * count = 0 does nothing).  The two agree bit for bit. */
 double sup_ltor_exp(double x);
 int sup_ltor_exp_device(const double* x, uint64_t count, double* out, int device_id);
+
+/* Torontonian tables (ABI 25): every click pattern of one list of n distinct
+ * modes from one walk.  f(z) depends on the selected positions only, so for
+ * every sub-list S of the list tor(O, S) = sum_{Z in S} (-1)^(|S| - |Z|) f(Z):
+ * the walk stores raw[z] = f(z) (unsigned, bit b of z = list position b, the
+ * bits of sup_torontonian_range(.., z, z + 1) up to its sign) and the subset
+ * Moebius transform, in place and bits ascending,
+ *   for b = 0 .. n-1: for every z with bit b set: t[z] = t[z] - t[z ^ (1 << b)]
+ * (one IEEE subtraction each; superman_amd/csrc/tortab.hpp)
+ * turns the table into all 2^n torontonians for the price of one.
+ * out: 2^n doubles.  transform = 0: out = raw.  transform != 0: out[mask] =
+ * the (loop) torontonian of the sub-list of the positions in mask, out[0] = 1.
+ * Bit-identical on the device (the table forms of walk_tor.hip / walk_ltor.hip,
+ * then mobius.hip), for any queue group, any pass shape and on host threads
+ * (on_cpu = 1).  A pivot that is not positive makes raw[z] NaN, which reaches
+ * exactly the masks that contain z.
+ * Errors, all before any device work: a null pointer, n outside [1, 32], a
+ * mode outside [0, M) or named twice, o->gpu_num > 1 (a table is one device's,
+ * o->device_id), a SUP_MOBIUS_BITS the transform was not compiled for:
+ * SUP_EINVAL; n above SUP_TORONTONIAN_TABLE_MAX_N on either path:
+ * SUP_EUNSUPPORTED; no device with on_cpu = 0: SUP_ENODEV.
+ * st: leaves = 1, gray_steps = visited_steps = 2^n, kernel_ms = prepare + walk
+ * + transform, est_ops_per_step = the entry's census + n / 2. */
+#define SUP_TORONTONIAN_TABLE_MAX_N 28   /* 2 GiB of results */
+int sup_torontonian_table(const double* O, int M, const int32_t* modes, int n, int transform, const sup_opts* o,
+                          int on_cpu, double* out, sup_stats* st);
+int sup_loop_torontonian_table(const double* O, int M, const double* gamma, const int32_t* modes, int n, int transform,
+                               const sup_opts* o, int on_cpu, double* out, sup_stats* st);
+/* The transform alone on t[0 .. 2^n), in place, n in [0, 28], on device
+ * o->device_id or (on_cpu = 1) host threads; exported for the test harness.
+ * The environment knob SUP_MOBIUS_BITS=L,K (read per call) forces a smaller
+ * tile (2^L doubles per work-group) and fewer bits per further pass (K) than
+ * the compiled defaults; the bits do not depend on it. */
+int sup_mobius_subsets(double* t, int n, const sup_opts* o, int on_cpu);
 
 /* Nijenhuis-Wilf prologue (gpu_exact_dense.cu:642-652): x0[j] = a[j][n-1] - rowsum_j/2,
  * p0 = prod x0.  Host-only helper, exported for the test harness. */

@@ -28,6 +28,8 @@ __all__ = [
            "torontonian", "torontonian_batch", "torontonian_range", "torontonian_plan", "TORONTONIAN_MAX_DEVICE_N",
            "loop_torontonian", "loop_torontonian_batch", "loop_torontonian_range", "loop_torontonian_plan",
            "LOOP_TORONTONIAN_MAX_DEVICE_N", "ltor_exp", "threshold_detection_prob", "threshold_detection_probs",
+           "torontonian_table", "loop_torontonian_table", "subset_mobius", "TORONTONIAN_TABLE_MAX_N",
+           "MOBIUS_TILE_BITS", "MOBIUS_PASS_BITS", "threshold_detection_distribution", "threshold_detection_sample",
            "perman_complex_fock_minors_plan","perman_complex_minors", "perman_complex_minors_submatrices", "perman_complex_minors_range", "boson_sample", "read_mtx_complex", "partial", "perman_shard", "plan_info", "plan_census", "CENSUS_CLASSES", "plan_key", "prepare", "read_matrix", "read_mtx", "sort_order",
     "skip_order", "compress", "decompose", "perman_reduced", "approx", "grid_graph", "ALGOS_APPROX",
     "nw_start", "device_count", "rccl_devices", "layout", "ShardCall", "SupError", "ALGOS_DENSE", "ALGOS_SPARSE",
@@ -1132,6 +1134,114 @@ def ltor_exp(x, device: bool = False, device_id: int = 0):
         for i in range(flat.shape[0]):
             out[i] = lib.sup_ltor_exp(float(flat[i]))
     return float(out[0]) if a.ndim == 0 else out.reshape(a.shape)
+
+
+# include/superman.h SUP_TORONTONIAN_TABLE_MAX_N: the most modes a table takes
+# (2^28 doubles = 2 GiB of results), on the device and on host threads
+TORONTONIAN_TABLE_MAX_N = 28
+# superman_amd/csrc/tortab.hpp: the transform's compiled shape (2^L doubles per
+# work-group tile, K bits per further pass); SUP_MOBIUS_BITS=L,K forces smaller
+MOBIUS_TILE_BITS = 12
+MOBIUS_PASS_BITS = 6
+
+
+def _tor_table(O, gamma, modes, transform, device_id, cpu, threads, return_stats):
+    o = _tor_matrix(O)
+    g = None if gamma is None else _ltor_gamma(gamma, o)
+    i32, count, n, single = _tor_lists(np.arange(o.shape[0] // 2) if modes is None else modes)
+    if not single:
+        raise ValueError("a torontonian table takes one list of modes of shape [n]")
+    lib = _lib.load()
+    op = _opts(gpu_num=1, device_id=device_id, threads=threads)
+    # above the cap the entry refuses before it writes: no 2^n buffer for it
+    out, st = np.zeros(1 << n if n <= TORONTONIAN_TABLE_MAX_N else 1), SupStats()
+    if g is None:
+        rc = lib.sup_torontonian_table(o.ctypes.data, o.shape[0] // 2, i32.ctypes.data, n, int(bool(transform)),
+                                       C.byref(op), int(bool(cpu)), out.ctypes.data, C.byref(st))
+    else:
+        rc = lib.sup_loop_torontonian_table(o.ctypes.data, o.shape[0] // 2, g.ctypes.data, i32.ctypes.data, n,
+                                            int(bool(transform)), C.byref(op), int(bool(cpu)), out.ctypes.data,
+                                            C.byref(st))
+    _lib.check(rc, "torontonian_table" if g is None else "loop_torontonian_table")
+    return (out, st.as_dict()) if return_stats else out
+
+
+def torontonian_table(O, modes=None, transform: bool = True, device_id: int = 0, cpu: bool = False, threads: int = 16,
+                      return_stats: bool = False):
+    """The torontonians of EVERY sub-list of one list of distinct modes
+    (default: all M) from one walk (sup_torontonian_table): an array of 2^n
+    doubles, entry ``mask`` = ``tor`` on the list positions whose bits ``mask``
+    has, entry 0 = 1.  ``transform=False`` gives the raw table f(z) =
+    1 / sqrt det(I - O_z) the walk stores; the subset Moebius transform
+    (``subset_mobius``) of it is the result.  One device or (cpu=True) the host
+    twin, bit-identical; n <= ``TORONTONIAN_TABLE_MAX_N``.  A subset that is not
+    positive definite makes exactly the masks that contain it NaN."""
+    return _tor_table(O, None, modes, transform, device_id, cpu, threads, return_stats)
+
+
+def loop_torontonian_table(O, gamma, modes=None, transform: bool = True, device_id: int = 0, cpu: bool = False,
+                           threads: int = 16, return_stats: bool = False):
+    """``torontonian_table`` for loop torontonians (sup_loop_torontonian_table):
+    entry ``mask`` = ``ltor`` of O and gamma on the list positions in ``mask``."""
+    return _tor_table(O, gamma, modes, transform, device_id, cpu, threads, return_stats)
+
+
+def subset_mobius(t, cpu: bool = False, device_id: int = 0, threads: int = 16):
+    """The subset Moebius transform of a table of 2^n doubles
+    (sup_mobius_subsets): out[S] = sum over Z in S of (-1)^(|S| - |Z|) t[Z], by
+    the stages b = 0 .. n-1 ascending, ``t[z] -= t[z ^ (1 << b)]`` where z has
+    bit b: one subtraction each, the same bits on the device (mobius.hip) and on
+    host threads.  Returns a new array."""
+    a = np.ascontiguousarray(np.asarray(t, dtype=np.float64)).reshape(-1).copy()
+    n = int(a.shape[0]).bit_length() - 1
+    if a.shape[0] < 1 or a.shape[0] != 1 << n:
+        raise ValueError(f"expected 2^n values, got {a.shape[0]}")
+    op = _opts(gpu_num=1, device_id=device_id, threads=threads)
+    _lib.check(_lib.load().sup_mobius_subsets(a.ctypes.data, n, C.byref(op), int(bool(cpu))), "subset_mobius")
+    return a
+
+
+def _threshold_reduce(mu, cov, modes):
+    """mu and cov (xxpp) of the listed modes alone: the others traced out."""
+    cov = np.asarray(cov, dtype=np.float64)
+    if cov.ndim != 2 or cov.shape[0] != cov.shape[1] or cov.shape[0] < 2 or cov.shape[0] % 2:
+        raise ValueError(f"expected a 2M x 2M covariance matrix with M >= 1, got shape {cov.shape}")
+    M = cov.shape[0] // 2
+    if modes is None:
+        return mu, cov
+    m = np.asarray(modes, dtype=np.int64).reshape(-1)
+    if m.size < 1 or np.any(m < 0) or np.any(m >= M) or np.unique(m).size != m.size:
+        raise ValueError(f"modes must be distinct integers in [0, {M}), got {modes}")
+    ix = np.concatenate([m, m + M])
+    return (None if mu is None else np.asarray(mu, dtype=np.float64)[ix]), cov[np.ix_(ix, ix)]
+
+
+def threshold_detection_distribution(mu, cov, modes=None, hbar: float = 2.0, **kw):
+    """The probabilities of ALL 2^n click patterns of the listed modes (default:
+    all M; the others are traced out) of the Gaussian state ``mu``, ``cov``
+    (xxpp ordering) on threshold detectors, from one (loop) torontonian table:
+    bit b of the index is the click on ``modes[b]``.  ``mu=None``: no
+    displacement, through ``torontonian_table``.  ``kw`` goes to the table call
+    (cpu, threads, device_id)."""
+    mu_r, cov_r = _threshold_reduce(mu, cov, modes)
+    O, gamma, pre = _threshold_setup(mu_r, cov_r, hbar)
+    tab = torontonian_table(O, **kw) if gamma is None else loop_torontonian_table(O, gamma, **kw)
+    return pre * tab
+
+
+def threshold_detection_sample(mu, cov, nsamples: int, seed: int, modes=None, hbar: float = 2.0, **kw):
+    """``nsamples`` exact click patterns (uint8 [nsamples, n], column b = the
+    click on ``modes[b]``) of the state on threshold detectors, by the inverse
+    CDF over ``threshold_detection_distribution``: negative roundings count as
+    0, and the uniform numbers are ``numpy.random.default_rng(seed)``'s.  The
+    samples are a function of the table's bits: the same on the device and
+    with ``cpu=True``."""
+    p = threshold_detection_distribution(mu, cov, modes=modes, hbar=hbar, **kw)
+    n = int(p.shape[0]).bit_length() - 1
+    cdf = np.cumsum(np.clip(p, 0.0, None))
+    u = np.random.default_rng(seed).random(int(nsamples)) * cdf[-1]
+    idx = np.minimum(np.searchsorted(cdf, u, side="right"), p.shape[0] - 1)
+    return ((idx[:, None] >> np.arange(n)[None, :]) & 1).astype(np.uint8)
 
 
 def _threshold_setup(mu, cov, hbar):

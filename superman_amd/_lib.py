@@ -47,6 +47,7 @@ EXPORTS = [
     "sup_hafnian_complex_pt", "sup_loop_hafnian_complex_pt", "sup_hafnian_complex_pt_range", "sup_hafnian_complex_pt_plan",
     "sup_torontonian", "sup_torontonian_range", "sup_torontonian_plan",
     "sup_loop_torontonian", "sup_loop_torontonian_range", "sup_loop_torontonian_plan", "sup_ltor_exp", "sup_ltor_exp_device",
+    "sup_torontonian_table", "sup_loop_torontonian_table", "sup_mobius_subsets",
     "sup_gpu_perman64_xshared_coalescing_mshared",
     "sup_gpu_perman64_xshared_coalescing_mshared_multigpu",
     "sup_gpu_perman64_xshared_coalescing_mshared_multigpucpu_chunks",
@@ -141,7 +142,7 @@ def load() -> C.CDLL:
             build()
         lib = C.CDLL(LIB_PATH)
         _declare(lib)
-        if lib.sup_abi_version() != 24:
+        if lib.sup_abi_version() != 25:
             raise RuntimeError("libsuperman_hip.so ABI version mismatch")
         _lib = lib
         return lib
@@ -217,6 +218,9 @@ def _declare(lib: C.CDLL) -> None:
     lib.sup_ltor_exp.argtypes = [D]
     lib.sup_ltor_exp.restype = D
     lib.sup_ltor_exp_device.argtypes = [P, C.c_uint64, P, I]
+    lib.sup_torontonian_table.argtypes = [P, I, P, I, I, C.POINTER(SupOpts), I, P, C.POINTER(SupStats)]
+    lib.sup_loop_torontonian_table.argtypes = [P, I, P, P, I, I, C.POINTER(SupOpts), I, P, C.POINTER(SupStats)]
+    lib.sup_mobius_subsets.argtypes = [P, I, C.POINTER(SupOpts), I]
     lib.sup_read_mtx_complex.argtypes = [C.c_char_p, C.POINTER(P), C.POINTER(I), C.POINTER(I)]
     lib.sup_perman_shard.argtypes = [P, I, I, I, I, I, C.POINTER(SupOpts), C.POINTER(D), C.POINTER(SupStats)]
     lib.sup_plan_info.argtypes = [P, I, I, I, C.POINTER(SupOpts), C.POINTER(I), P, C.POINTER(I), C.POINTER(I),

@@ -11,6 +11,7 @@
 #include "hafnian_pt.hpp"
 #include "loop_torontonian.hpp"
 #include "torontonian.hpp"
+#include "torontonian_table.hpp"
 
 using namespace sup;
 
@@ -854,6 +855,50 @@ int sup_ltor_exp_device(const double* x, uint64_t count, double* out, int device
     return SUP_EINVAL;
   }
   return run_ltor_exp(device_id, x, count, out);
+}
+
+static int torontonian_table_entry(const LtorIn& in, bool loop, int n, int transform, const sup_opts* o_in, int on_cpu,
+                                   double* out, sup_stats* st) {
+  auto t0 = std::chrono::steady_clock::now();
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  TorInfo ti;
+  if (int rc = torontonian_table(in, loop, n, transform != 0, o, on_cpu != 0, out, &ti)) return rc;
+  if (st) {
+    std::memset(st, 0, sizeof(*st));
+    st->kernel_ms = ti.kernel_ms;
+    st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    st->gray_steps = ti.subsets;
+    st->visited_steps = ti.subsets;
+    st->devices_used = ti.devices;
+    st->grid = ti.grid;
+    st->walk_kind = (int)kWalkDense;
+    st->leaves = 1;
+    st->est_ops_per_step = ti.ops;
+  }
+  return SUP_OK;
+}
+
+int sup_torontonian_table(const double* O, int M, const int32_t* modes, int n, int transform, const sup_opts* o,
+                          int on_cpu, double* out, sup_stats* st) {
+  LtorIn in;
+  in.O = O, in.M = M, in.modes = modes;
+  return torontonian_table_entry(in, false, n, transform, o, on_cpu, out, st);
+}
+
+int sup_loop_torontonian_table(const double* O, int M, const double* gamma, const int32_t* modes, int n, int transform,
+                               const sup_opts* o, int on_cpu, double* out, sup_stats* st) {
+  LtorIn in;
+  in.O = O, in.M = M, in.gamma = gamma, in.modes = modes;
+  return torontonian_table_entry(in, true, n, transform, o, on_cpu, out, st);
+}
+
+int sup_mobius_subsets(double* t, int n, const sup_opts* o_in, int on_cpu) {
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  return mobius_subsets(t, n, o, on_cpu != 0);
 }
 
 // sup_stats of a minors call: the batch entry's, with the one-walk step cost.

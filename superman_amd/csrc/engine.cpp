@@ -7,6 +7,7 @@
 #include "hafnian_pt.hpp"
 #include "loop_torontonian.hpp"
 #include "torontonian.hpp"
+#include "torontonian_table.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -1803,6 +1804,111 @@ int run_loop_torontonian(int dev, const LtorIn& in, int n, uint64_t first, uint6
   SUP_HIP(hipMemcpyAsync(out, c->d_cbout, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, s));
   if (grid_out) *grid_out = (int)geo.grid;
   return timed_sync(c, kernel_ms);
+}
+
+// A table of 2^n doubles lives in d_cbout; one above kTableKeepBytes is given
+// back after the call instead of staying with the context.
+constexpr size_t kTableKeepBytes = (size_t)256 << 20;
+static void release_table(DeviceCtx* c) {
+  if (c->cbout_cap * sizeof(double) <= kTableKeepBytes) return;
+  (void)hipFree(c->d_cbout);
+  c->d_cbout = nullptr;
+  c->cbout_cap = 0;
+}
+
+// Torontonian table (walk_tor.hip's and walk_ltor.hip's table forms, then
+// mobius.hip) of the one list in.modes: O (and gamma behind it) and the list go
+// up, prepare gathers the matrix on the device, the table walk stores f(z) of
+// every z, the transform's passes follow on the same stream, and one download
+// brings the 2^n doubles into out.
+int run_torontonian_table(int dev, const LtorIn& in, bool loop, int n, bool transform, int L, int K, double* out,
+                          double* kernel_ms, int* grid_out) {
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (grid_out) *grid_out = 0;
+  if (n < 1 || n > kTorTabMaxN || (loop ? ltor_lds_bytes(n) : tor_lds_bytes(n)) > 65536 || !out || !in.O || !in.modes ||
+      (loop && !in.gamma) || in.M < 1) {
+    set_error("run_torontonian_table: bad request");
+    return SUP_EINVAL;
+  }
+  const int llog = tor_chunk_log(n);
+  const uint64_t total = 1ull << n, cm = (total + (1ull << llog) - 1) >> llog;
+  const uint64_t g_doubles = loop ? ltor_g_doubles(n) : tor_g_doubles(n);
+  const size_t o_doubles = (size_t)8 * in.M * in.M, gm_doubles = loop ? (size_t)4 * in.M : 0;
+  CtxGuard guard;
+  int rc = guard.open(dev, "device buffers");
+  if (rc) return rc;
+  DeviceCtx* c = guard.c;
+  int occ = 0;
+  SUP_HIP(loop ? ltor_table_occupancy(n, &occ) : tor_table_occupancy(n, &occ));
+  if ((rc = ensure(c->d_cbtab, c->cbtab_cap, (size_t)g_doubles))) return rc;
+  if ((rc = ensure(c->d_cbidx, c->cbidx_cap, (size_t)n))) return rc;
+  if ((rc = ensure(c->d_cbU, c->cbU_cap, o_doubles + gm_doubles))) return rc;
+  if ((rc = ensure(c->d_cbout, c->cbout_cap, (size_t)total))) return rc;
+  hipStream_t s = c->stream;
+  c->tables_uid = 0;  // the walk leaves head 0 nonzero
+  c->head_zero[0] = false;
+  SUP_HIP(hipMemcpyAsync(c->d_cbU, in.O, o_doubles * sizeof(double), hipMemcpyHostToDevice, s));
+  if (loop) SUP_HIP(hipMemcpyAsync(c->d_cbU + o_doubles, in.gamma, gm_doubles * sizeof(double), hipMemcpyHostToDevice, s));
+  SUP_HIP(hipMemcpyAsync(c->d_cbidx, in.modes, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  SUP_HIP(hipMemsetAsync(c->d_counter, 0, sizeof(unsigned), s));
+  const uint64_t resident = (uint64_t)c->cus * (uint64_t)std::max(occ, 1);
+  const char* fg = std::getenv("SUP_WALK_GROUP");  // tests, read per call: chunks per ticket (the bits do not change)
+  const LaunchGeom geo = walk_geometry(cm, resident, 1, false, fg ? std::max(1, std::atoi(fg)) : 0);
+  TorParams p{};
+  p.G = c->d_cbtab;
+  p.chunk_count = cm;
+  p.chunk_out = c->d_cbout;
+  p.counter = c->d_counter;
+  p.group = geo.group;
+  p.n = (unsigned)n;
+  p.nn = (unsigned)tor_nn(n);
+  p.llog = (unsigned)llog;
+  p.cm = (unsigned)cm;
+  p.z_begin = 0;
+  p.z_end = total;
+  p.chunk_first = 0;
+  SUP_HIP(hipEventRecord(c->ev0, s));
+  SUP_ON_DEVICE(c->dev, "torontonian table launch");
+  if (loop) {
+    SUP_HIP(launch_ltor_prepare(c->d_cbU, in.M, c->d_cbU + o_doubles, c->d_cbidx, n, 1, c->d_cbtab, s));
+    SUP_HIP(launch_ltor_table(p, (int)geo.grid, s));
+  } else {
+    SUP_HIP(launch_tor_prepare(c->d_cbU, in.M, c->d_cbidx, n, 1, c->d_cbtab, s));
+    SUP_HIP(launch_tor_table(p, (int)geo.grid, s));
+  }
+  if (transform) SUP_HIP(launch_mobius(c->d_cbout, n, L, K, c->cus * 8, s));
+  SUP_HIP(hipEventRecord(c->ev1, s));
+  SUP_HIP(hipMemcpyAsync(out, c->d_cbout, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (grid_out) *grid_out = (int)geo.grid;
+  rc = timed_sync(c, kernel_ms);
+  release_table(c);
+  return rc;
+}
+
+// t[0 .. 2^n) up, mobius.hip's passes, and down again (sup_mobius_subsets).
+int run_mobius(int dev, double* t, int n, int L, int K) {
+  if (!t || n < 0 || n > kTorTabMaxN) {
+    set_error("run_mobius: bad request");
+    return SUP_EINVAL;
+  }
+  if (n == 0) return SUP_OK;
+  const uint64_t total = 1ull << n;
+  CtxGuard guard;
+  int rc = guard.open(dev, "device buffers");
+  if (rc) return rc;
+  DeviceCtx* c = guard.c;
+  if ((rc = ensure(c->d_cbout, c->cbout_cap, (size_t)total))) return rc;
+  hipStream_t s = c->stream;
+  SUP_HIP(hipMemcpyAsync(c->d_cbout, t, (size_t)total * sizeof(double), hipMemcpyHostToDevice, s));
+  SUP_HIP(hipEventRecord(c->ev0, s));
+  SUP_ON_DEVICE(c->dev, "mobius launch");
+  SUP_HIP(launch_mobius(c->d_cbout, n, L, K, c->cus * 8, s));
+  SUP_HIP(hipEventRecord(c->ev1, s));
+  SUP_HIP(hipMemcpyAsync(t, c->d_cbout, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, s));
+  double ms = 0.0;
+  rc = timed_sync(c, &ms);
+  release_table(c);
+  return rc;
 }
 
 // out[i] = ltor_exp(x[i]) on the device (sup_ltor_exp_device), in the

@@ -57,6 +57,9 @@
 // same file and the complex 2M x 1 MatrixMarket file g.mtx (coordinate or
 // array); prints "Loop torontonian: <value>".  --loop without --gamma, or
 // --gamma without --torontonian --loop, is an error.
+// --torontonian --table [--raw] [--loop --gamma g.mtx] [--modes ...]: the table
+// of every sub-list's (loop) torontonian from one walk (sup_torontonian_table;
+// --raw: the untransformed f(z)); prints 2^n lines "mask %.17e".
 #include <getopt.h>
 
 #include <chrono>
@@ -78,7 +81,7 @@ struct Cli {
   bool generic = true, dense = true, approximation = false, gpu = false, cpu = false, grid_graph = false;
   bool rccl = false, verbose = false, compression = false, exact = false, quad = false;
   bool half_calc = false, half_store = false, complex = false, complex_quad = false, complex_exact = false, preprocessing_given = false, gpu_num_given = false;
-  bool hafnian = false, loop = false, powertrace = false, torontonian = false;
+  bool hafnian = false, loop = false, powertrace = false, torontonian = false, table = false, raw = false;
   int gpu_num = 2, threads = 16, perman_algo = 1, preprocessing = 0, device = 0, reps = 1;
   double scaling = -1.0;
   long number_of_times = 100000;  // main.cu:338-344 defaults
@@ -344,6 +347,36 @@ bool read_gamma(const std::string& path, int N, std::vector<double>& g) {
   return true;
 }
 
+// --torontonian --table [--raw]: sup_torontonian_table (--loop:
+// sup_loop_torontonian_table) of the list; 2^n lines "mask value".  Frees mat.
+int run_torontonian_table_cli(const Cli& c, double* mat, int M, const std::vector<int32_t>& modes,
+                              const std::vector<double>& gamma, const sup_opts& o) {
+  const int n = (int)modes.size();
+  if (n > SUP_TORONTONIAN_TABLE_MAX_N) {
+    std::fprintf(stderr, "perman: --table takes at most %d modes (got %d)\n", SUP_TORONTONIAN_TABLE_MAX_N, n);
+    sup_free(mat);
+    return 1;
+  }
+  std::vector<double> tab((size_t)1 << n);
+  sup_stats st;
+  int rc = SUP_OK;
+  const auto t0 = std::chrono::steady_clock::now();
+  for (int rep = 0; rep < c.reps && rc == SUP_OK; ++rep)
+    rc = c.loop ? sup_loop_torontonian_table(mat, M, gamma.data(), modes.data(), n, c.raw ? 0 : 1, &o, c.gpu ? 0 : 1,
+                                             tab.data(), &st)
+                : sup_torontonian_table(mat, M, modes.data(), n, c.raw ? 0 : 1, &o, c.gpu ? 0 : 1, tab.data(), &st);
+  const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / (double)c.reps;
+  sup_free(mat);
+  if (rc != SUP_OK) return fail(c.loop ? "loop torontonian table" : "torontonian table");
+  std::cout << "Result: " << (c.gpu ? "gpu_" : "cpu_") << (c.loop ? "loop_torontonian_table64 " : "torontonian_table64 ")
+            << tab.size() << " entries in " << sec << std::endl;
+  for (size_t mask = 0; mask < tab.size(); ++mask) std::printf("%zu %.17e\n", mask, tab[mask]);
+  if (c.verbose)
+    std::printf("Stats: devices %d kernel_ms %.3f wall_ms %.3f subsets %llu grid %d\n", st.devices_used, st.kernel_ms,
+                st.wall_ms, (unsigned long long)st.visited_steps, st.grid);
+  return 0;
+}
+
 // --torontonian: sup_torontonian of a Hermitian MatrixMarket `complex` file of
 // even order (--loop --gamma: sup_loop_torontonian); the line shape follows --hafnian.
 int run_torontonian_cli(const Cli& c) {
@@ -366,6 +399,10 @@ int run_torontonian_cli(const Cli& c) {
   }
   if (!c.loop && !c.gamma.empty()) {
     std::fprintf(stderr, "perman: --gamma goes with --torontonian --loop\n");
+    return 1;
+  }
+  if (c.raw && !c.table) {
+    std::fprintf(stderr, "perman: --raw goes with --torontonian --table\n");
     return 1;
   }
   double* mat = nullptr;
@@ -408,6 +445,7 @@ int run_torontonian_cli(const Cli& c) {
   o.gpu_num = 1;
   o.device_id = c.device;
   o.threads = c.threads;
+  if (c.table) return run_torontonian_table_cli(c, mat, M, modes, gamma, o);
   double out = 0.0;
   sup_stats st;
   int rc = SUP_OK;
@@ -457,6 +495,8 @@ int main(int argc, char** argv) {
                                         {"torontonian", 0, NULL, 1007},
                                         {"modes", 1, NULL, 1008},
                                         {"gamma", 1, NULL, 1009},
+                                        {"table", 0, NULL, 1010},
+                                        {"raw", 0, NULL, 1011},
                                         {NULL, 0, NULL, 0}};
   int opt;
   auto need_arg = [&](char o) -> bool {
@@ -502,6 +542,8 @@ int main(int argc, char** argv) {
       case 1007: c.torontonian = true; break;
       case 1008: c.modes = optarg; break;
       case 1009: c.gamma = optarg; break;
+      case 1010: c.table = true; break;
+      case 1011: c.raw = true; break;
       case 'v': c.verbose = true; break;
       // v2 flags (revised_perman/main.cpp:1431-1460): -w stores the matrix in
       // single precision (the permanent of the float-rounded entries); -h asks
@@ -530,6 +572,10 @@ int main(int argc, char** argv) {
   for (int i = optind; i < argc; ++i) std::printf("Non-option argument %s\n", argv[i]);
   if (!c.cpu && !c.gpu) c.gpu = true;  // main.cu:482-484
   if (c.torontonian) return run_torontonian_cli(c);
+  if (c.table || c.raw) {
+    std::fprintf(stderr, "perman: --table and --raw go with --torontonian\n");
+    return 1;
+  }
   if (!c.modes.empty()) {
     std::fprintf(stderr, "perman: --modes goes with --torontonian\n");
     return 1;

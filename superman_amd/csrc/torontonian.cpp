@@ -148,6 +148,29 @@ void tor_gather(const TorIn& in, const int32_t* s, int n, std::vector<double>& G
 
 }  // namespace
 
+// The raw table of one list (tortab.hpp): out[z] = f(z) for every z in [0,
+// 2^n), runs of 2^9 consecutive z over the threads, each from nothing and then
+// with the rows the previous subset shares (the bits do not depend on the cut).
+void tor_table_raw_cpu(const TorIn& in, int n, int threads, double* out) {
+  const int nn = tor_nn(n);
+  std::vector<double> G;
+  tor_gather(in, in.modes, n, G);
+  const uint64_t total = 1ull << n, run = std::min<uint64_t>(total, 512), runs = total / run;
+  const int T = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::max(threads, 1), runs));
+  std::atomic<uint64_t> next{0};
+  auto work = [&]() {
+    TorState S(nn);
+    for (uint64_t a = next.fetch_add(1); a < runs; a = next.fetch_add(1)) {
+      S.have = false;
+      for (uint64_t z = a * run; z < (a + 1) * run; ++z) out[z] = tor_f(G.data(), nn, S, z);
+    }
+  };
+  std::vector<std::thread> th;
+  for (int w = 1; w < T; ++w) th.emplace_back(work);
+  work();
+  for (auto& t : th) t.join();
+}
+
 int torontonian_plan(int n, uint64_t* subsets, double* est_ops) {
   if (n < 1 || n > kTorMaxN) {
     set_error("sup_torontonian_plan: n = " + std::to_string(n) + " outside [1, 32]");

@@ -26,6 +26,7 @@
 #include "cx.hpp"
 #include "loop_torontonian.hpp"
 #include "ltor.hpp"
+#include "tortab.hpp"
 #include "walk_common.hpp"
 
 namespace sup {
@@ -165,7 +166,11 @@ __device__ __forceinline__ double ltor_tail(const double* S, double f, uint32_t 
   return f * ltor_exp(-0.5 * d);
 }
 
-__global__ __launch_bounds__(kLtorBlock) void walk_ltor(TorParams p) {
+// TABLE (tortab.hpp): the lane that holds z stores its unsigned f(z) to
+// chunk_out[z], the 2^n table of the one list, and the sign, the butterfly, the
+// chunk partial and the fold are left out.
+template <bool TABLE>
+__device__ __forceinline__ void walk_ltor_body(const TorParams& p) {
   extern __shared__ double ltor_lds[];
   const uint32_t lane = threadIdx.x;
   const uint32_t n = p.n, nn = p.nn, H = nn - (uint32_t)kLtorW, PM = 2u * H, N = 2u * nn;
@@ -205,20 +210,24 @@ __global__ __launch_bounds__(kLtorBlock) void walk_ltor(TorParams p) {
         if (z >= zlo && z < zhi) {
           const uint32_t q = lane >> kLtorW;
           f = ltor_tail(m.S + 2 * (size_t)q * kLtorE, m.ps[q], lane & ((1u << kLtorW) - 1u));
-          if ((n - (uint32_t)__builtin_popcountll(z)) & 1u) f = -f;
+          if (TABLE) p.chunk_out[z] = f;
+          else if ((n - (uint32_t)__builtin_popcountll(z)) & 1u) f = -f;
         }
-        acc = acc + ltor_wave_sum(f);
+        if (!TABLE) acc = acc + ltor_wave_sum(f);
         __syncthreads();  // the next group's advance overwrites S
       }
       if (lane == j) keepv = acc;
     }
     const uint64_t a = (uint64_t)g * p.group + lane;
-    if (lane < p.group && a < p.chunk_count) {
+    if (!TABLE && lane < p.group && a < p.chunk_count) {
       p.chunk_out[2 * a] = keepv;
       p.chunk_out[2 * a + 1] = 0.0;
     }
   }
 }
+
+__global__ __launch_bounds__(kLtorBlock) void walk_ltor(TorParams p) { walk_ltor_body<false>(p); }
+__global__ __launch_bounds__(kLtorBlock) void walk_ltor_table(TorParams p) { walk_ltor_body<true>(p); }
 
 // ltor_prepare: one block per list writes its gathered matrix (tor.hpp
 // tor_entry) and border row (ltor.hpp ltor_border), the host twin's own
@@ -255,6 +264,19 @@ hipError_t launch_ltor(const TorParams& p, int grid, hipStream_t s) {
   if (!ltor_params_ok(p) || grid < 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(walk_ltor, dim3(grid), dim3(kLtorBlock), ltor_lds_bytes((int)p.n), s, p);
   return hipGetLastError();
+}
+
+// p.chunk_out: the 2^n doubles of the one list's table.
+hipError_t launch_ltor_table(const TorParams& p, int grid, hipStream_t s) {
+  if (!ltor_params_ok(p) || grid < 1 || p.n > (unsigned)kTorTabMaxN || p.chunk_count != p.cm || p.z_begin != 0 ||
+      p.z_end != (1ull << p.n))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(walk_ltor_table, dim3(grid), dim3(kLtorBlock), ltor_lds_bytes((int)p.n), s, p);
+  return hipGetLastError();
+}
+
+hipError_t ltor_table_occupancy(int n, int* blocks_per_cu) {
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, walk_ltor_table, kLtorBlock, ltor_lds_bytes(n));
 }
 
 hipError_t ltor_occupancy(int n, int* blocks_per_cu) {

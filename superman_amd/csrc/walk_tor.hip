@@ -28,6 +28,7 @@
 #include "cx.hpp"
 #include "tor.hpp"
 #include "torontonian.hpp"
+#include "tortab.hpp"
 #include "walk_common.hpp"
 
 namespace sup {
@@ -155,7 +156,11 @@ __device__ __forceinline__ double tor_tail(const double* S, double f, uint32_t b
   return f;
 }
 
-__global__ __launch_bounds__(kTorBlock) void walk_tor(TorParams p) {
+// TABLE (tortab.hpp): the lane that holds z stores its unsigned f(z) to
+// chunk_out[z], the 2^n table of the one list, and the sign, the butterfly, the
+// chunk partial and the fold are left out.
+template <bool TABLE>
+__device__ __forceinline__ void walk_tor_body(const TorParams& p) {
   extern __shared__ double tor_lds[];
   const uint32_t lane = threadIdx.x;
   const uint32_t n = p.n, nn = p.nn, H = nn - (uint32_t)kTorW, PM = 2u * H, N = 2u * nn;
@@ -195,20 +200,24 @@ __global__ __launch_bounds__(kTorBlock) void walk_tor(TorParams p) {
         if (z >= zlo && z < zhi) {
           const uint32_t q = lane >> kTorW;
           f = tor_tail(m.S + 2 * (size_t)q * kTorE, m.ps[q], lane & ((1u << kTorW) - 1u));
-          if ((n - (uint32_t)__builtin_popcountll(z)) & 1u) f = -f;
+          if (TABLE) p.chunk_out[z] = f;
+          else if ((n - (uint32_t)__builtin_popcountll(z)) & 1u) f = -f;
         }
-        acc = acc + tor_wave_sum(f);
+        if (!TABLE) acc = acc + tor_wave_sum(f);
         __syncthreads();  // the next group's advance overwrites S
       }
       if (lane == j) keepv = acc;
     }
     const uint64_t a = (uint64_t)g * p.group + lane;
-    if (lane < p.group && a < p.chunk_count) {
+    if (!TABLE && lane < p.group && a < p.chunk_count) {
       p.chunk_out[2 * a] = keepv;
       p.chunk_out[2 * a + 1] = 0.0;
     }
   }
 }
+
+__global__ __launch_bounds__(kTorBlock) void walk_tor(TorParams p) { walk_tor_body<false>(p); }
+__global__ __launch_bounds__(kTorBlock) void walk_tor_table(TorParams p) { walk_tor_body<true>(p); }
 
 // tor_prepare: one block per list writes its gathered matrix (tor.hpp
 // tor_entry, the host twin's own function) from O and the list.
@@ -244,6 +253,19 @@ hipError_t launch_tor(const TorParams& p, int grid, hipStream_t s) {
   if (!tor_params_ok(p) || grid < 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(walk_tor, dim3(grid), dim3(kTorBlock), tor_lds_bytes((int)p.n), s, p);
   return hipGetLastError();
+}
+
+// p.chunk_out: the 2^n doubles of the one list's table.
+hipError_t launch_tor_table(const TorParams& p, int grid, hipStream_t s) {
+  if (!tor_params_ok(p) || grid < 1 || p.n > (unsigned)kTorTabMaxN || p.chunk_count != p.cm || p.z_begin != 0 ||
+      p.z_end != (1ull << p.n))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(walk_tor_table, dim3(grid), dim3(kTorBlock), tor_lds_bytes((int)p.n), s, p);
+  return hipGetLastError();
+}
+
+hipError_t tor_table_occupancy(int n, int* blocks_per_cu) {
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, walk_tor_table, kTorBlock, tor_lds_bytes(n));
 }
 
 hipError_t tor_occupancy(int n, int* blocks_per_cu) {

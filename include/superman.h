@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SUP_ABI_VERSION 25  /* 25: sup_torontonian_table, sup_loop_torontonian_table, sup_mobius_subsets, SUP_TORONTONIAN_TABLE_MAX_N; 24: sup_loop_torontonian, sup_loop_torontonian_range, sup_loop_torontonian_plan, sup_ltor_exp, sup_ltor_exp_device, SUP_LOOP_TORONTONIAN_MAX_DEVICE_N; 23: sup_hafnian_complex_exact; 22: sup_torontonian, sup_torontonian_range, sup_torontonian_plan, SUP_TORONTONIAN_MAX_DEVICE_N; 21: sup_hafnian_complex_pt, sup_loop_hafnian_complex_pt, sup_hafnian_complex_pt_range, sup_hafnian_complex_pt_plan, SUP_HAFNIAN_PT_MAX_DEVICE_N; 20: sup_hafnian_complex, sup_loop_hafnian_complex, sup_hafnian_complex_plan; 19: sup_perman_complex_exact, sup_perman_complex_exact_range, SUP_CPLX_EXACT_MAX_DEVICE_N; 18: sup_perman_complex_quad, sup_perman_complex_quad_range, SUP_CPLX_QUAD_MAX_DEVICE_N; 17:sup_perman_complex_fock_minors, sup_perman_complex_fock_minors_plan, sup_boson_sample_fock; 16: sup_plan_census; 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
+#define SUP_ABI_VERSION 26  /* 26: sup_loop_hafnian_complex_each, sup_gbs_sample; 25: sup_torontonian_table, sup_loop_torontonian_table, sup_mobius_subsets, SUP_TORONTONIAN_TABLE_MAX_N; 24: sup_loop_torontonian, sup_loop_torontonian_range, sup_loop_torontonian_plan, sup_ltor_exp, sup_ltor_exp_device, SUP_LOOP_TORONTONIAN_MAX_DEVICE_N; 23: sup_hafnian_complex_exact; 22: sup_torontonian, sup_torontonian_range, sup_torontonian_plan, SUP_TORONTONIAN_MAX_DEVICE_N; 21: sup_hafnian_complex_pt, sup_loop_hafnian_complex_pt, sup_hafnian_complex_pt_range, sup_hafnian_complex_pt_plan, SUP_HAFNIAN_PT_MAX_DEVICE_N; 20: sup_hafnian_complex, sup_loop_hafnian_complex, sup_hafnian_complex_plan; 19: sup_perman_complex_exact, sup_perman_complex_exact_range, SUP_CPLX_EXACT_MAX_DEVICE_N; 18: sup_perman_complex_quad, sup_perman_complex_quad_range, SUP_CPLX_QUAD_MAX_DEVICE_N; 17:sup_perman_complex_fock_minors, sup_perman_complex_fock_minors_plan, sup_boson_sample_fock; 16: sup_plan_census; 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SUP_OK            0
@@ -727,6 +727,65 @@ int sup_loop_hafnian_complex(const double* A, int M, const double* mu, const int
 /* The terms T of each matrix's sum, host only (no device).  terms may be NULL.
  * A null list or n outside [1, 64]: SUP_EINVAL.  Indices are only compared. */
 int sup_hafnian_complex_plan(const int32_t* idx, int n, uint64_t count, uint64_t* terms);
+
+/* Ragged loop hafnians with a displacement per item (ABI 26): the batch one
+ * chain-rule step of a PNR Gaussian boson sampler needs.  A as above; mu holds
+ * nmu rows of M complex; item k, k < count, is the loop hafnian of the gather of
+ * A by idx[k stride .. k stride + n[k]) with row mu_of[k] of mu on the diagonal
+ * (mu_of NULL: row k), 0 <= n[k] <= 64 and stride >= max n[k] (entries past
+ * n[k] are not read).  Item k with n[k] >= 1 has the bits of
+ * sup_loop_hafnian_complex(A, M, mu + 2 M mu_of[k], idx + stride k, n[k], 1, ..);
+ * an item with n[k] = 0 is exactly 1 + 0i and walks nothing.  The whole call
+ * is one slab queue (slabs as sup_hafnian_complex; SUP_HAFNIAN_SLAB): items of
+ * different order sit next to each other in the wave-chunk queue, and the
+ * kernel (walk_lhafe.hip) reads the order, the Horner bound and the
+ * coefficient row per matrix.  Bit-identical on the device, on
+ * any device count, for any slab size and queue group and on host threads.
+ * Errors, all before any device work: a null pointer (mu_of alone may be NULL),
+ * M < 1, a pair A[i][j], A[j][i] that differs, n[k] outside [0, 64], stride <
+ * n[k], mu_of[k] (or k) outside [0, nmu), an index outside [0, M): SUP_EINVAL
+ * with a message naming the place; an item of more than 2^24 wave-chunks:
+ * SUP_EUNSUPPORTED; no device with on_cpu = 0: SUP_ENODEV (no CPU fallback).
+ * st: leaves = count, gray_steps = sum_k 2^(n[k]-1) (nominal, saturating),
+ * visited_steps = sum_k T_k, kernel_ms, wall_ms, devices_used, grid,
+ * est_ops_per_step = the T-weighted census of DESIGN.md 8h over the items. */
+int sup_loop_hafnian_complex_each(const double* A, int M,
+                                  const double* mu, uint64_t nmu, /* nmu x M complex rows            */
+                                  const int32_t* mu_of,           /* count; NULL: item k uses row k  */
+                                  const int32_t* idx, int stride, /* count x stride, first n[k] used */
+                                  const int32_t* n,               /* count, each in [0, 64]          */
+                                  uint64_t count, const sup_opts* o, int on_cpu, double* out, sup_stats* st);
+/* A photon-number-resolving Gaussian boson sampler for pure states (ABI 26):
+ * the chain rule of Bulmer et al. 2022 on the entry above (gbs.cpp, DESIGN.md
+ * 8n).  B (M x M complex, symmetric bit for bit) and zeta[s] (M complex per
+ * sample) describe the state: <n|psi> is proportional to lhaf(B gathered with
+ * n_i copies of i, zeta on the diagonal) / sqrt(prod n_i!).  het[s] holds the
+ * heterodyne outcomes alpha_0 .. alpha_{M-1} of sample s, drawn by the caller
+ * from N(mean, V + (hbar/2) I): this entry draws nothing Gaussian and is
+ * deterministic.  For mode k = 0 .. M-1 of sample s
+ *   z_i = zeta_i + sum_{j > k} B_ij conj(alpha_j), i <= k   (j ascending, fma per part)
+ *   w_c = |lhaf(B; the outcomes so far, then c copies of k; z)|^2 / c!,  c <= cutoff
+ *   u   = (w64(seed, sample0 + s, step k) >> 11) 2^-53      (sup_boson_sample's w64)
+ *   n_k = the first c whose running sum of w exceeds u sum(w); a zero weight
+ *         is never chosen
+ * and every step is one sup_loop_hafnian_complex_each call per batch of
+ * samples.  A candidate whose order would exceed 64 has weight 0.  When the
+ * weights of a sample sum to zero or to a non-finite value, that mode and every
+ * later one are -1.  Renormalising over c <= cutoff is the only approximation:
+ * the law is exact as cutoff grows.  Sample s depends on (B, zeta[s], het[s],
+ * cutoff, seed, sample0 + s) only; the device and on_cpu = 1 draw identical
+ * samples.
+ * Errors: null B, M outside [1, 64], cutoff outside [0, 64], B not symmetric:
+ * SUP_EINVAL; then nsamples = 0 returns SUP_OK; a null zeta, het or out:
+ * SUP_EINVAL; no device with on_cpu = 0: SUP_ENODEV.
+ * st: leaves = nsamples, visited_steps = gray_steps = the sum of the calls'
+ * visited_steps, kernel_ms summed over the steps, est_ops_per_step (T-weighted
+ * over all calls), partials[0] / [1] = wall ms in the each-calls / in the host
+ * stage, partials[2] = samples that ended in -1. */
+int sup_gbs_sample(const double* B, int M,
+                   const double* zeta, const double* het, /* nsamples x M complex each */
+                   int cutoff, uint64_t nsamples, uint64_t sample0, uint64_t seed,
+                   const sup_opts* o, int on_cpu, int32_t* out /* nsamples x M */, sup_stats* st);
 
 /* Exact hafnians and loop hafnians of Gaussian-integer matrices (ABI 23): the
  * integer truth the floating hafnian entries are judged against, and exact

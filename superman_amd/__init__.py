@@ -11,6 +11,7 @@ fallback.  ``perman_cpu`` is the explicit CPU algorithm of the CLI's ``-c``.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -30,6 +31,8 @@ __all__ = [
            "LOOP_TORONTONIAN_MAX_DEVICE_N", "ltor_exp", "threshold_detection_prob", "threshold_detection_probs",
            "torontonian_table", "loop_torontonian_table", "subset_mobius", "TORONTONIAN_TABLE_MAX_N",
            "MOBIUS_TILE_BITS", "MOBIUS_PASS_BITS", "threshold_detection_distribution", "threshold_detection_sample",
+           "loop_hafnian_each", "gbs_pure_state", "pnr_detection_prob", "pnr_detection_probs", "gbs_sample",
+           "gbs_sample_chain",
            "perman_complex_fock_minors_plan","perman_complex_minors", "perman_complex_minors_submatrices", "perman_complex_minors_range", "boson_sample", "read_mtx_complex", "partial", "perman_shard", "plan_info", "plan_census", "CENSUS_CLASSES", "plan_key", "prepare", "read_matrix", "read_mtx", "sort_order",
     "skip_order", "compress", "decompose", "perman_reduced", "approx", "grid_graph", "ALGOS_APPROX",
     "nw_start", "device_count", "rccl_devices", "layout", "ShardCall", "SupError", "ALGOS_DENSE", "ALGOS_SPARSE",
@@ -1304,6 +1307,214 @@ def threshold_detection_probs(mu, cov, patterns, hbar: float = 2.0, **kw):
 def threshold_detection_prob(mu, cov, clicks, hbar: float = 2.0, **kw):
     """The probability of one click pattern (``threshold_detection_probs``)."""
     return threshold_detection_probs(mu, cov, np.asarray(clicks).reshape(-1), hbar=hbar, **kw)
+
+
+def loop_hafnian_each(A, mus, lists, mu_of=None, gpu_num: int = 1, device_id: int = 0, cpu: bool = False,
+                      threads: int = 16, return_stats: bool = False):
+    """The loop hafnians of ragged gathers of one complex symmetric matrix A,
+    each with its own displacement (sup_loop_hafnian_complex_each): item k is
+    the loop hafnian of ``A[np.ix_(lists[k], lists[k])]`` with
+    ``mus[mu_of[k]][lists[k]]`` on the diagonal (``mu_of=None``: row k).  The
+    lists may differ in length (0..64) and may repeat; an empty list gives
+    exactly 1.  One call is one queue on the device (walk_lhafe.hip) whatever
+    the orders, and item k has the bits of ``hafnian_batch(A, lists[k],
+    mu=mus[mu_of[k]], loop=True)``.  complex128 array of shape [count]."""
+    a = np.ascontiguousarray(np.asarray(A, dtype=np.complex128))
+    if a.ndim != 2 or a.shape[0] != a.shape[1] or a.shape[0] < 1:
+        raise ValueError(f"expected a non-empty square matrix A, got shape {a.shape}")
+    M = a.shape[0]
+    m = np.ascontiguousarray(np.asarray(mus, dtype=np.complex128))
+    if m.ndim == 1:
+        m = m[None, :]
+    if m.ndim != 2 or m.shape[1] != M or m.shape[0] < 1:
+        raise ValueError(f"mus must have shape [nmu, {M}] with nmu >= 1, got {m.shape}")
+    rows = [np.asarray(l).reshape(-1) for l in lists]
+    count = len(rows)
+    n32 = np.array([r.size for r in rows] + [0], dtype=np.int64)
+    if n32.max() > 64:
+        raise ValueError(f"a list has {int(n32.max())} entries, more than 64 (64-bit Gray index)")
+    flat = np.concatenate([r for r in rows if r.size]) if n32.sum() else np.zeros(0, np.int64)
+    if flat.size and not np.issubdtype(flat.dtype, np.integer):
+        raise ValueError(f"lists must hold integers, got dtype {flat.dtype}")
+    if flat.size and (flat.min() < -2**31 or flat.max() >= 2**31):
+        raise ValueError("lists hold an index outside the 32-bit range")
+    stride = max(int(n32.max()), 1)
+    idx = np.zeros((max(count, 1), stride), np.int32)
+    if flat.size:  # row k's entries at idx[k, :n[k]]
+        first = np.cumsum(n32[:count]) - n32[:count]
+        idx[np.repeat(np.arange(count), n32[:count]), np.arange(flat.size) - np.repeat(first, n32[:count])] = flat
+    n32 = np.ascontiguousarray(n32[:max(count, 1)], dtype=np.int32)
+    of = None
+    if mu_of is not None:
+        ofa = np.asarray(mu_of)
+        if ofa.shape != (count,) or (count and not np.issubdtype(ofa.dtype, np.integer)):
+            raise ValueError(f"mu_of must hold one integer per list, got shape {ofa.shape}")
+        if count and (ofa.min() < -2**31 or ofa.max() >= 2**31):
+            raise ValueError("mu_of holds a row outside the 32-bit range")
+        of = np.ascontiguousarray(ofa, dtype=np.int32) if count else np.zeros(1, np.int32)
+    lib = _lib.load()
+    o = _opts(gpu_num=gpu_num, device_id=device_id, threads=threads)
+    out, st = np.zeros(2 * max(count, 1)), SupStats()
+    rc = lib.sup_loop_hafnian_complex_each(a.ctypes.data, M, m.ctypes.data, m.shape[0],
+                                           None if of is None else of.ctypes.data, idx.ctypes.data, stride,
+                                           n32.ctypes.data, count, C.byref(o), int(bool(cpu)), out.ctypes.data,
+                                           C.byref(st))
+    _lib.check(rc, "loop_hafnian_each")
+    v = _batch_result(out, count)
+    return (v, st.as_dict()) if return_stats else v
+
+
+def gbs_pure_state(mu, cov, hbar: float = 2.0):
+    """``(B, zeta, p0)`` of a pure Gaussian state with mean ``mu`` (or None) and
+    covariance ``cov`` (xxpp ordering, vacuum = hbar / 2), from
+    ``_threshold_setup``'s O, gamma and prefactor: with Abar = X O (X swaps the
+    two M-blocks), B = Abar[M:, M:] (symmetrised), zeta = gamma[:M] and
+    <n|psi> = sqrt(p0) lhaf(B gathered with n_i copies of i, zeta) /
+    sqrt(prod n_i!) up to one global phase.  The state is pure exactly when the
+    off-diagonal M x M blocks of Abar vanish: ValueError when they exceed 1e-8
+    of max |Abar| (and 1e-14, the rounding of O = I - Q^-1 whose parts are of
+    order one: the vacuum's Abar is nothing but that rounding)."""
+    O, gamma, pre = _threshold_setup(mu, cov, hbar)
+    M = O.shape[0] // 2
+    # Abar = X O: the rows of O with the two blocks swapped
+    off = max(np.abs(O[M:, M:]).max(), np.abs(O[:M, :M]).max())
+    if off > max(1e-8 * np.abs(O).max(), 1e-14):
+        raise ValueError(f"the state is not pure: the off-diagonal blocks of Abar reach {off:.3e}")
+    B = O[:M, M:]
+    B = np.ascontiguousarray((B + B.T) / 2.0)
+    zeta = np.zeros(M, np.complex128) if gamma is None else np.ascontiguousarray(gamma[:M])
+    return B, zeta, pre
+
+
+def _pnr_patterns(patterns, M):
+    pat = np.asarray(patterns)
+    single = pat.ndim == 1
+    if single:
+        pat = pat[None, :]
+    if pat.ndim != 2 or pat.shape[1] != M or (pat.size and not np.issubdtype(pat.dtype, np.integer)) or (pat < 0).any():
+        raise ValueError(f"patterns must hold non-negative integers with shape [M] or [count, M], M = {M}; "
+                         f"got shape {np.shape(patterns)}")
+    return pat.astype(np.int64), single
+
+
+def pnr_detection_probs(mu, cov, patterns, hbar: float = 2.0, **kw):
+    """The probabilities of photon-number patterns (shape [count, M], or one
+    pattern of shape [M]) of the Gaussian state with mean ``mu`` (or None) and
+    covariance ``cov`` (xxpp ordering, vacuum = hbar / 2) on
+    photon-number-resolving detectors.  A pure state (``gbs_pure_state``
+    accepts it) takes one ragged ``loop_hafnian_each`` call at order N = the
+    pattern's photon total: p = p0 |lhaf(B, zeta)|^2 / prod n_i!.  Any other
+    state takes p = p0 lhaf(Abar, conj(gamma)) / prod n_i! on the list with i
+    and i + M n_i times each, order 2N: one ``hafnian_batch`` call per photon
+    total (``mu=None``: the plain hafnian).  The all-zero pattern is p0 alone.
+    ``kw`` goes to those calls (cpu, threads, gpu_num, device_id)."""
+    O, gamma, pre = _threshold_setup(mu, cov, hbar)
+    M = O.shape[0] // 2
+    pat, single = _pnr_patterns(patterns, M)
+    tot = pat.sum(1)
+    fac = np.array([float(np.prod([math.factorial(int(v)) for v in p])) for p in pat])
+    out = np.zeros(pat.shape[0])
+    try:
+        B, zeta, _ = gbs_pure_state(mu, cov, hbar)
+    except ValueError:
+        B = None
+    if B is not None:
+        if tot.size and tot.max() > 64:
+            raise ValueError(f"a pattern holds {int(tot.max())} photons, more than 64")
+        lists = [np.repeat(np.arange(M), p) for p in pat]
+        v = loop_hafnian_each(B, zeta[None, :], lists, mu_of=np.zeros(len(lists), np.int32), **kw)
+        out = pre * (v.real * v.real + v.imag * v.imag) / fac
+    else:
+        if tot.size and tot.max() > 32:
+            raise ValueError(f"a pattern holds {int(tot.max())} photons, more than 32 (order 2N <= 64)")
+        Abar = np.concatenate([O[M:], O[:M]])
+        Abar = np.ascontiguousarray((Abar + Abar.T) / 2.0)
+        for N in np.unique(tot):
+            which = np.nonzero(tot == N)[0]
+            if N == 0:
+                continue
+            idx = np.stack([np.repeat(np.concatenate([np.arange(M), np.arange(M) + M]), np.concatenate([pat[i], pat[i]]))
+                            for i in which]).astype(np.int32)
+            if gamma is None:
+                v = hafnian_batch(Abar, idx, **kw)
+            else:
+                v = hafnian_batch(Abar, idx, mu=np.conj(gamma), loop=True, **kw)
+            out[which] = pre * np.asarray(v).real / fac[which]
+    out[tot == 0] = pre  # the empty pattern: the prefactor alone
+    return float(out[0]) if single else out
+
+
+def pnr_detection_prob(mu, cov, pattern, hbar: float = 2.0, **kw):
+    """The probability of one photon-number pattern (``pnr_detection_probs``)."""
+    return pnr_detection_probs(mu, cov, np.asarray(pattern).reshape(-1), hbar=hbar, **kw)
+
+
+def gbs_sample_chain(B, zeta, het, seed: int, cutoff: int = 8, sample0: int = 0, gpu_num: int = 1, device_id: int = 0,
+                     cpu: bool = False, threads: int = 16, return_stats: bool = False):
+    """The deterministic part of the PNR sampler (sup_gbs_sample): the chain
+    rule over the modes for the pure state ``B`` (M x M symmetric), ``zeta``
+    ([nsamples, M], or [M] for every sample) and the heterodyne outcomes ``het``
+    ([nsamples, M] complex).  Every mode step is one ragged loop-hafnian call
+    per batch of samples.  Row s depends on (B, zeta[s], het[s], cutoff, seed,
+    sample0 + s) only.  int32 [nsamples, M]; -1 from the mode on at which a
+    sample's weights summed to zero or to a non-finite value."""
+    b = np.ascontiguousarray(np.asarray(B, dtype=np.complex128))
+    if b.ndim != 2 or b.shape[0] != b.shape[1] or b.shape[0] < 1:
+        raise ValueError(f"expected a non-empty square matrix B, got shape {b.shape}")
+    M = b.shape[0]
+    h = np.ascontiguousarray(np.asarray(het, dtype=np.complex128))
+    if h.ndim != 2 or h.shape[1] != M:
+        raise ValueError(f"het must have shape [nsamples, {M}], got {h.shape}")
+    ns = h.shape[0]
+    z = np.asarray(zeta, dtype=np.complex128)
+    if z.shape == (M,):
+        z = np.broadcast_to(z, (ns, M))
+    if z.shape != (ns, M):
+        raise ValueError(f"zeta must have shape [{M}] or [{ns}, {M}], got {z.shape}")
+    z = np.ascontiguousarray(z)
+    if sample0 < 0:
+        raise ValueError("sample0 must be >= 0")
+    lib = _lib.load()
+    o = _opts(gpu_num=gpu_num, device_id=device_id, threads=threads)
+    out, st = np.zeros((max(ns, 1), M), np.int32), SupStats()
+    hp = h.ctypes.data if ns else out.ctypes.data
+    zp = z.ctypes.data if ns else out.ctypes.data
+    _lib.check(lib.sup_gbs_sample(b.ctypes.data, M, zp, hp, int(cutoff), ns, int(sample0),
+                                  int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(o), int(bool(cpu)), out.ctypes.data,
+                                  C.byref(st)), "gbs_sample")
+    v = out[:ns].copy()
+    if not return_stats:
+        return v
+    d = st.as_dict()
+    d["each_ms"], d["host_ms"], d["failed"] = float(st.partials[0]), float(st.partials[1]), int(st.partials[2])
+    return v, d
+
+
+def gbs_sample(mu, cov, nsamples: int, seed: int, cutoff: int = 8, hbar: float = 2.0, sample0: int = 0, **kw):
+    """``nsamples`` photon-number patterns (int32 [nsamples, M]) of the pure
+    Gaussian state ``mu`` (or None), ``cov`` (xxpp ordering) on
+    photon-number-resolving detectors, by the chain rule of Bulmer et al. 2022:
+    the heterodyne outcomes are ``numpy.random.default_rng(seed)
+    .standard_normal((sample0 + nsamples, 2M))`` times the Cholesky factor of
+    cov + (hbar / 2) I plus the mean, rows [sample0, sample0 + nsamples), and
+    the rest is ``gbs_sample_chain``.  Mode k is drawn from its conditional law
+    renormalised over 0..cutoff: the only approximation, exact as the cutoff
+    grows.  Mixed states raise ValueError (``gbs_pure_state``).  The same
+    samples on the device and with ``cpu=True``; rows drawn in pieces with
+    ``sample0`` equal the whole run's.  ``kw`` goes to ``gbs_sample_chain``."""
+    B, zeta, _ = gbs_pure_state(mu, cov, hbar)
+    M = B.shape[0]
+    nsamples, sample0 = int(nsamples), int(sample0)
+    if nsamples < 0 or sample0 < 0:
+        raise ValueError("nsamples and sample0 must be >= 0")
+    V = np.asarray(cov, dtype=np.float64)
+    L = np.linalg.cholesky(V + (float(hbar) / 2.0) * np.eye(2 * M))
+    g = np.random.default_rng(seed).standard_normal((sample0 + nsamples, 2 * M))[sample0:]
+    xp = g @ L.T
+    if mu is not None:
+        xp = xp + np.asarray(mu, dtype=np.float64)[None, :]
+    het = (xp[:, :M] + 1j * xp[:, M:]) / np.sqrt(2.0 * float(hbar))
+    return gbs_sample_chain(B, zeta, het, seed, cutoff=cutoff, sample0=sample0, **kw)
 
 
 def partial(mat, start: int, end: int, kernel: str = "dense", gpu_num: int = 1, device_id: int = 0,

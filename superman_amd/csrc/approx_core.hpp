@@ -60,6 +60,12 @@ SUP_HD Philox4 draw(uint64_t seed, uint64_t sample, uint32_t step) {
                        (uint32_t)(seed >> 32));
 }
 
+// The 64-bit word of a draw the samplers use (boson.cpp, gbs.cpp): v[0] | v[1] << 32.
+SUP_HD uint64_t word64(uint64_t seed, uint64_t s, uint32_t step) {
+  const Philox4 d = draw(seed, s, step);
+  return (uint64_t)d.v[0] | ((uint64_t)d.v[1] << 32);
+}
+
 SUP_HD int popc64(uint64_t x) { return __builtin_popcountll(x); }
 
 // Position of the k-th (0-based) set bit of x (k < popcount(x)).

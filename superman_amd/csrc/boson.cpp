@@ -52,11 +52,6 @@ namespace sup {
 
 namespace {
 
-uint64_t word64(uint64_t seed, uint64_t s, uint32_t step) {
-  const Philox4 d = draw(seed, s, step);
-  return (uint64_t)d.v[0] | ((uint64_t)d.v[1] << 32);
-}
-
 // fn(first, last) over [0, count) split into contiguous ranges on up to T threads.
 template <class Fn>
 void parallel_ranges(uint64_t count, int T, const Fn& fn) {

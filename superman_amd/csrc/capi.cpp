@@ -659,6 +659,63 @@ int sup_hafnian_complex_plan(const int32_t* idx, int n, uint64_t count, uint64_t
   return hafnian_plan(idx, n, count, terms);
 }
 
+int sup_loop_hafnian_complex_each(const double* A, int M, const double* mu, uint64_t nmu, const int32_t* mu_of,
+                                  const int32_t* idx, int stride, const int32_t* n, uint64_t count,
+                                  const sup_opts* o_in, int on_cpu, double* out, sup_stats* st) {
+  auto t0 = std::chrono::steady_clock::now();
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  HafEachIn in;
+  in.A = A, in.M = M, in.mu = mu, in.nmu = nmu, in.mu_of = mu_of, in.idx = idx, in.stride = stride, in.n = n;
+  HafInfo hi;
+  if (int rc = loop_hafnian_each(in, count, o, on_cpu != 0, out, &hi)) return rc;
+  if (st) {
+    std::memset(st, 0, sizeof(*st));
+    st->kernel_ms = hi.kernel_ms;
+    st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    uint64_t nominal = 0;  // the sums without repeats, saturating
+    for (uint64_t k = 0; k < count; ++k)
+      if (n[k] > 0) {
+        const uint64_t add = 1ull << (n[k] - 1);
+        nominal = nominal + add < nominal ? ~0ull : nominal + add;
+      }
+    st->gray_steps = nominal;
+    st->visited_steps = hi.terms;
+    st->devices_used = hi.devices;
+    st->grid = hi.grid;
+    st->walk_kind = (int)kWalkDense;
+    st->leaves = (int)std::min<uint64_t>(count, 0x7fffffffu);
+    st->est_ops_per_step = hi.ops;
+  }
+  return SUP_OK;
+}
+
+int sup_gbs_sample(const double* B, int M, const double* zeta, const double* het, int cutoff, uint64_t nsamples,
+                   uint64_t sample0, uint64_t seed, const sup_opts* o_in, int on_cpu, int32_t* out, sup_stats* st) {
+  auto t0 = std::chrono::steady_clock::now();
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  GbsInfo gi;
+  if (int rc = gbs_sample(B, M, zeta, het, cutoff, nsamples, sample0, seed, o, on_cpu != 0, out, &gi)) return rc;
+  if (st) {
+    std::memset(st, 0, sizeof(*st));
+    st->kernel_ms = gi.kernel_ms;
+    st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    st->gray_steps = gi.visited;
+    st->visited_steps = gi.visited;
+    st->devices_used = gi.devices;
+    st->walk_kind = (int)kWalkDense;
+    st->leaves = (int)std::min<uint64_t>(nsamples, 0x7fffffffu);
+    st->est_ops_per_step = gi.ops;
+    st->partials[0] = gi.each_ms;         // wall time inside the ragged loop-hafnian calls
+    st->partials[1] = gi.host_ms;         // wall time of the host stage: lists, z rows, weights and draws
+    st->partials[2] = (double)gi.failed;  // samples whose weights summed to zero or to a non-finite value
+  }
+  return SUP_OK;
+}
+
 int sup_hafnian_complex_exact(const double* A, int M, const double* mu, const int32_t* idx, int n, uint64_t count,
                               const sup_opts* o_in, int on_cpu, char* out_re, char* out_im, size_t out_len,
                               sup_stats* st) {

@@ -1415,14 +1415,19 @@ int run_cplx_fock_minors(int dev, const FockSlab& S, const CplxBatchIn& in, doub
 // the device), the walk over the slab's queue and the per-matrix fold run on
 // the context's stream with no host work between them, and one download
 // brings 16 bytes per matrix into out.  The buffers are the collision-aware
-// walk's (same context lock).
+// walk's (same context lock).  A ragged slab (S.each; walk_lhafe.hip) sends up
+// the displacement rows it reads and one row number per matrix, and its walk
+// and prepare kernels take the order, the coefficient row and the
+// displacement per matrix.
 int run_hafnian(int dev, const HafSlab& S, const HafIn& in, double* out, double* kernel_ms, int* grid_out) {
   if (kernel_ms) *kernel_ms = 0.0;
   if (grid_out) *grid_out = 0;
   const uint64_t K = S.mats.size(), chunks = S.chunks.size();
   if (K == 0) return SUP_OK;
-  if (S.n < 1 || S.n > SUP_MAX_N || (!S.loop && (S.n & 1)) || chunks == 0 || chunks > 0x7fffffffull || !out || !in.A ||
-      in.M < 1 || (S.loop && (!in.mu || S.coef.size() != (size_t)S.n / 2 + 1))) {
+  const bool shape_ok =
+      S.each ? S.n == 0 && S.loop && S.mu_row.size() == K && S.mu_rows >= 1 && S.mu_lo >= 0 && !S.coef.empty()
+             : S.n >= 1 && S.n <= SUP_MAX_N && (S.loop || !(S.n & 1)) && (!S.loop || S.coef.size() == (size_t)S.n / 2 + 1);
+  if (!shape_ok || chunks == 0 || chunks > 0x7fffffffull || !out || !in.A || in.M < 1 || (S.loop && !in.mu)) {
     set_error("run_hafnian: bad request");
     return SUP_EINVAL;
   }
@@ -1435,14 +1440,17 @@ int run_hafnian(int dev, const HafSlab& S, const HafIn& in, double* out, double*
   const size_t u_wts = u_chunks + units(chunks * sizeof(FockChunk));
   const size_t u_grp = u_wts + units(wts.size() * sizeof(double));
   const size_t u_coef = u_grp + units(S.grp.size() * sizeof(int32_t));
-  const size_t u_end = u_coef + units(S.coef.size() * sizeof(double)) + 1;
-  const size_t a_doubles = (size_t)2 * in.M * in.M, mu_doubles = S.loop ? (size_t)2 * in.M : 0;
+  const size_t u_murow = u_coef + units(S.coef.size() * sizeof(double));
+  const size_t u_end = u_murow + units(S.mu_row.size() * sizeof(int32_t)) + 1;
+  const size_t a_doubles = (size_t)2 * in.M * in.M;
+  const size_t mu_doubles = S.each ? (size_t)2 * in.M * (size_t)S.mu_rows : S.loop ? (size_t)2 * in.M : 0;
+  const double* mu_src = S.each ? in.mu + (size_t)2 * in.M * (size_t)S.mu_lo : in.mu;
   CtxGuard guard;
   int rc = guard.open(dev, "device buffers");
   if (rc) return rc;
   DeviceCtx* c = guard.c;
   int occ = 0;
-  SUP_HIP(haf_occupancy(S.loop, &occ));
+  SUP_HIP(S.each ? lhafe_occupancy(&occ) : haf_occupancy(S.loop, &occ));
   if ((rc = ensure(c->d_cbtab, c->cbtab_cap, (size_t)S.tab_doubles))) return rc;
   if ((rc = ensure(c->d_cbU, c->cbU_cap, a_doubles + mu_doubles))) return rc;
   if ((rc = ensure(c->d_chunk, c->chunk_cap, (size_t)(2 * chunks)))) return rc;
@@ -1455,7 +1463,8 @@ int run_hafnian(int dev, const HafSlab& S, const HafIn& in, double* out, double*
     return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
   };
   SUP_HIP(up(c->d_cbU, in.A, a_doubles * sizeof(double)));
-  SUP_HIP(up(c->d_cbU + a_doubles, in.mu, mu_doubles * sizeof(double)));
+  SUP_HIP(up(c->d_cbU + a_doubles, mu_src, mu_doubles * sizeof(double)));
+  SUP_HIP(up(c->d_fock + u_murow, S.mu_row.data(), S.mu_row.size() * sizeof(int32_t)));
   SUP_HIP(up(c->d_fock + u_grp, S.grp.data(), S.grp.size() * sizeof(int32_t)));
   SUP_HIP(up(c->d_fock + u_prog, S.prog.data(), S.prog.size() * sizeof(HafStep)));
   SUP_HIP(up(c->d_fock + u_dig, S.dig.data(), S.dig.size() * sizeof(HafDigit)));
@@ -1482,9 +1491,16 @@ int run_hafnian(int dev, const HafSlab& S, const HafIn& in, double* out, double*
   p.n = (unsigned)S.n;
   SUP_HIP(hipEventRecord(c->ev0, s));
   SUP_ON_DEVICE(c->dev, "hafnian walk launch");
-  SUP_HIP(launch_haf_prepare(c->d_cbU, in.M, S.loop ? c->d_cbU + a_doubles : nullptr,
-                             reinterpret_cast<const int32_t*>(c->d_fock + u_grp), p.mats, K, c->d_cbtab, s));
-  SUP_HIP(launch_haf(S.loop, p, (int)geo.grid, s));
+  if (S.each) {
+    SUP_HIP(launch_lhafe_prepare(c->d_cbU, in.M, c->d_cbU + a_doubles,
+                                 reinterpret_cast<const int32_t*>(c->d_fock + u_murow),
+                                 reinterpret_cast<const int32_t*>(c->d_fock + u_grp), p.mats, K, c->d_cbtab, s));
+    SUP_HIP(launch_lhafe(p, (int)geo.grid, s));
+  } else {
+    SUP_HIP(launch_haf_prepare(c->d_cbU, in.M, S.loop ? c->d_cbU + a_doubles : nullptr,
+                               reinterpret_cast<const int32_t*>(c->d_fock + u_grp), p.mats, K, c->d_cbtab, s));
+    SUP_HIP(launch_haf(S.loop, p, (int)geo.grid, s));
+  }
   SUP_HIP(launch_haf_fold(c->d_chunk, p.mats, K, S.div, c->d_cbout, s));
   SUP_HIP(hipEventRecord(c->ev1, s));
   SUP_HIP(hipMemcpyAsync(out, c->d_cbout, (size_t)(K * 2) * sizeof(double), hipMemcpyDeviceToHost, s));

@@ -751,6 +751,12 @@ struct HafSlab {
   std::vector<FockChunk> chunks;
   std::vector<double> coef;  // loop form: 1 / (j! (n - 2j)!)
   double div = 1.0;          // m! (hafnian) or 1 (loop hafnian)
+  // A ragged slab (loop_hafnian_each): n = 0, every matrix carries its order
+  // and its coefficient row in HafMat::ord, coef is the pool of those rows, and
+  // matrix k reads row mu_lo + mu_row[k] of the caller's displacement rows.
+  bool each = false;
+  std::vector<int32_t> mu_row;
+  int64_t mu_lo = 0, mu_rows = 0;  // the rows the slab reads: [mu_lo, mu_lo + mu_rows)
 };
 // Prepares (tables from in.A, in.mu and the slab's groups), walks and folds
 // slab S on device `dev`: out[2k], out[2k + 1] = the (loop) hafnian of its
@@ -781,5 +787,38 @@ int haf_check_request(const HafIn& in, int n, uint64_t count, const std::string&
 // first matrix not taken.  host_tables: write haf_entry's tables into S.tabs.
 uint64_t haf_fill_slab(HafSlab& S, const HafIn& in, int n, uint64_t k, uint64_t kend, uint64_t slab_max,
                        size_t partial_bytes, bool host_tables);
+
+// ---- ragged loop hafnians and the PNR sampler on them (hafnian.cpp, gbs.cpp; walk_lhafe.hip) ----
+// Item k is the loop hafnian of the gather of A by idx[k stride .. + n[k]) with
+// row mu_of[k] (null: row k) of mu (nmu x M complex) on the diagonal.
+struct HafEachIn {
+  const double* A = nullptr;
+  int M = 0;
+  const double* mu = nullptr;
+  uint64_t nmu = 0;
+  const int32_t* mu_of = nullptr;
+  const int32_t* idx = nullptr;
+  int stride = 0;
+  const int32_t* n = nullptr;
+};
+// out[2k], out[2k + 1] = item k (sup_loop_hafnian_complex_each): the bits of
+// hafnian_complex on that item alone, exactly 1 at n[k] = 0; the items of a
+// call share slabs (one queue per slab) whatever their orders.  Everything is
+// checked before any work.
+int loop_hafnian_each(const HafEachIn& in, uint64_t count, const sup_opts& o, bool on_cpu, double* out, HafInfo* info);
+// The bytes an item of order n >= 1 with list idx adds to a slab, and the cap
+// loop_hafnian_each fills a slab to.
+size_t haf_item_bytes(const int32_t* idx, int n);
+size_t haf_slab_cap_bytes();
+struct GbsInfo {
+  double kernel_ms = 0.0, each_ms = 0.0, host_ms = 0.0;
+  int devices = 0;
+  uint64_t visited = 0, failed = 0;
+  double ops = 0.0;  // the T-weighted mean of haf_ops over every call's items
+};
+// nsamples PNR outcomes of the pure Gaussian state (B, zeta[s]) by the chain
+// rule with the heterodyne outcomes het (sup_gbs_sample; gbs.cpp).
+int gbs_sample(const double* B, int M, const double* zeta, const double* het, int cutoff, uint64_t nsamples,
+               uint64_t sample0, uint64_t seed, const sup_opts& o, bool on_cpu, int32_t* out, GbsInfo* info);
 
 }  // namespace sup

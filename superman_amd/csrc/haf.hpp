@@ -61,7 +61,7 @@ struct HafMat {
   uint32_t K;       // distinct values
   uint32_t grp;     // grp index: K (value, multiplicity) pairs, then the group of each digit
   uint32_t pairs;   // pairs in the table
-  uint32_t pad_;
+  uint32_t ord;     // ragged slabs (walk_lhafe.hip): the matrix's order n | its coef row's offset (doubles) << 8; else 0
 };
 
 struct HafParams {
@@ -71,12 +71,12 @@ struct HafParams {
   const double* wts;
   const HafMat* mats;
   const FockChunk* chunks;
-  const double* coef;  // loop form: 1 / (j! (n - 2j)!), j <= n / 2
+  const double* coef;  // loop form: 1 / (j! (n - 2j)!), j <= n / 2 (ragged slabs: the pool of those rows, HafMat::ord)
   unsigned long long chunk_count;
   double* chunk_out;      // 2 doubles (re, im) per wave-chunk
   unsigned int* counter;  // queue head (zeroed before launch)
   unsigned int group;     // chunks per ticket (1..64)
-  unsigned int n;
+  unsigned int n;         // the order of every matrix (ragged slabs: unused, HafMat::ord)
 };
 
 inline uint32_t haf_pairs(int W, int ND) {

@@ -9,6 +9,13 @@
 // what walk_haf.hip reads, and the host twin reads the same arrays, running the
 // same operations in the same order: chunk partials, fock_fold per matrix,
 // (2 x the sum) / m!.  Result k is a function of (A, mu, idx[k]) only.
+//
+// sup_loop_hafnian_complex_each (loop_hafnian_each below) builds
+// the same slabs from items whose orders and displacement rows differ: the
+// order and the coefficient row travel per matrix in HafMat::ord, the row of mu
+// per matrix in HafSlab::mu_row, and walk_lhafe.hip and the host twin read them
+// there.  Item k is a function of (A, its row of mu, its list) only, with the
+// bits of sup_loop_hafnian_complex on it alone.
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
@@ -88,8 +95,10 @@ uint32_t haf_program(HafSlab& S, const FockLayout& l, HafProgs& progs) {
 }
 
 // Appends the matrix with groups and layout c to S.  host_tables: write the
-// table here (the host twin); the device path leaves it to haf_prepare.
-void haf_append(HafSlab& S, const HafIn& in, const HafChoice& c, HafProgs& progs, bool host_tables) {
+// table here (the host twin) with displacement mu (null: the plain hafnian);
+// the device path leaves it to haf_prepare.  ord: HafMat::ord.
+void haf_append(HafSlab& S, const HafIn& in, const HafChoice& c, HafProgs& progs, bool host_tables, const double* mu,
+                uint32_t ord) {
   const FockLayout& l = c.lay;
   HafMat M{};
   M.tab = S.tab_doubles;
@@ -100,6 +109,7 @@ void haf_append(HafSlab& S, const HafIn& in, const HafChoice& c, HafProgs& progs
   M.H = (uint32_t)l.H;
   M.K = (uint32_t)c.g.K;
   M.pairs = haf_pairs(l.nwalk, l.nd - l.nwalk);
+  M.ord = ord;
   M.grp = (uint32_t)S.grp.size();
   for (int k = 0; k < c.g.K; ++k) S.grp.push_back(c.g.val[k]), S.grp.push_back(c.g.mult[k]);
   for (int d = 0; d < l.nd; ++d) S.grp.push_back(l.col[d]);
@@ -116,7 +126,7 @@ void haf_append(HafSlab& S, const HafIn& in, const HafChoice& c, HafProgs& progs
     double* t = S.tabs.data() + M.tab;
     const int32_t* g = S.grp.data() + M.grp;
     for (uint32_t e = 0; e < M.pairs; ++e) {
-      const cx v = haf_entry(in.A, in.M, in.loop ? in.mu : nullptr, g, (int)M.K, (int)M.W, (int)M.ndig, e);
+      const cx v = haf_entry(in.A, in.M, mu, g, (int)M.K, (int)M.W, (int)M.ndig, e);
       t[2 * (size_t)e] = v.re, t[2 * (size_t)e + 1] = v.im;
     }
   }
@@ -134,10 +144,12 @@ cx haf_chunk(const HafSlab& S, uint64_t a) {
   const double* tab = S.tabs.data() + M.tab;
   auto ld = [&](size_t pair) { return cx{tab[2 * pair], tab[2 * pair + 1]}; };
   const HafStep* prog = S.prog.data() + M.prog;
-  const uint32_t n = (uint32_t)S.n, m = n >> 1;
+  // a ragged slab's matrix carries its own order and coefficient row
+  const uint32_t n = S.each ? M.ord & 0xffu : (uint32_t)S.n, m = n >> 1;
+  const double* coef = S.coef.data() + (M.ord >> 8);
   const size_t hs = (size_t)kHafHigh + M.ndig, high0 = (size_t)kHafStart + 2 * (size_t)M.W * kHafRow;
   const int ge = M.W > 4u ? kHafWalkDigits : 4;  // the G entries the walk updates
-  auto term = [&](cx Q, cx r) { return S.loop ? haf_loop_poly(Q, r, S.coef.data(), n) : haf_pow(Q, m); };
+  auto term = [&](cx Q, cx r) { return S.loop ? haf_loop_poly(Q, r, coef, n) : haf_pow(Q, m); };
   cx v[64];
   for (uint32_t lane = 0; lane < 64; ++lane) {
     const uint32_t h = 64u * ck.local + lane;
@@ -223,7 +235,7 @@ uint64_t haf_fill_slab(HafSlab& S, const HafIn& in, int n, uint64_t k, uint64_t 
     const size_t add = haf_bytes(c, partial_bytes);
     const uint64_t chunks = (c.lay.H + 63) / 64;
     if (k > k0 && (bytes + add > kHafSlabCapBytes || S.chunks.size() + chunks > 0x7fffffffull)) break;
-    haf_append(S, in, c, progs, host_tables);
+    haf_append(S, in, c, progs, host_tables, in.loop ? in.mu : nullptr, 0u);
     bytes += add;
   }
   return k;
@@ -364,6 +376,190 @@ int hafnian_complex(const HafIn& in, int n, uint64_t count, const sup_opts& o, b
           if (drc[g]) derr[g] = last_error();
           dms[g] += ms;
         }
+      }
+    } catch (const std::bad_alloc&) {
+      derr[g] = "out of host memory for a slab's tables and partials";
+      drc[g] = SUP_ENOMEM;
+    }
+  };
+  std::vector<std::thread> th;
+  for (int g = 1; g < G; ++g) th.emplace_back(work, g);
+  work(0);
+  for (auto& t : th) t.join();
+  for (int g = 0; g < G; ++g)
+    if (drc[g]) {
+      set_error(derr[g]);
+      return drc[g];
+    }
+  if (!on_cpu) {
+    hi.kernel_ms = *std::max_element(dms.begin(), dms.end());
+    hi.grid = dgrid[0];
+    hi.devices = G;
+  }
+  if (info) *info = hi;
+  return SUP_OK;
+}
+
+// ---- the ragged batch: sup_loop_hafnian_complex_each ----
+
+size_t haf_item_bytes(const int32_t* idx, int n) { return haf_bytes(haf_choose(idx, n), 16); }
+size_t haf_slab_cap_bytes() { return kHafSlabCapBytes; }
+
+int loop_hafnian_each(const HafEachIn& in, uint64_t count, const sup_opts& o, bool on_cpu, double* out, HafInfo* info) {
+  const std::string who = "sup_loop_hafnian_complex_each";
+  if (!out || !in.A || !in.mu || !in.idx || !in.n) {
+    set_error(who + ": null pointer");
+    return SUP_EINVAL;
+  }
+  HafIn hin;
+  hin.A = in.A, hin.M = in.M, hin.mu = in.mu, hin.idx = in.idx, hin.loop = true;
+  if (int rc = haf_check_request(hin, 1, 0, who)) return rc;  // M and the symmetry of A: no list is read
+  for (uint64_t k = 0; k < count; ++k) {
+    const int32_t nk = in.n[k];
+    if (nk < 0 || nk > SUP_MAX_N) {
+      set_error(who + ": n[k = " + std::to_string(k) + "] = " + std::to_string(nk) + " outside [0, 64]");
+      return SUP_EINVAL;
+    }
+    if (nk > in.stride) {
+      set_error(who + ": stride = " + std::to_string(in.stride) + " < n[k = " + std::to_string(k) + "] = " +
+                std::to_string(nk));
+      return SUP_EINVAL;
+    }
+    const int64_t row = in.mu_of ? (int64_t)in.mu_of[k] : (int64_t)k;
+    if (row < 0 || (uint64_t)row >= in.nmu) {
+      set_error(who + ": mu_of[k = " + std::to_string(k) + "] = " + std::to_string(row) + " outside [0, " +
+                std::to_string(in.nmu) + ")");
+      return SUP_EINVAL;
+    }
+    for (int j = 0; j < nk; ++j) {
+      const int32_t v = in.idx[k * (uint64_t)in.stride + j];
+      if (v < 0 || v >= in.M) {
+        set_error(who + ": idx[k = " + std::to_string(k) + "][position " + std::to_string(j) + "] = " +
+                  std::to_string(v) + " outside [0, " + std::to_string(in.M) + ")");
+        return SUP_EINVAL;
+      }
+    }
+  }
+  HafInfo hi;
+  if (info) *info = hi;
+  // the items that walk: an item of order 0 is the empty product
+  std::vector<uint64_t> live;
+  for (uint64_t k = 0; k < count; ++k) {
+    if (in.n[k] > 0) live.push_back(k);
+    else out[2 * k] = 1.0, out[2 * k + 1] = 0.0;
+  }
+  const uint64_t L = live.size();
+  if (L == 0) return SUP_OK;
+  auto list_of = [&](uint64_t k) { return in.idx + k * (uint64_t)in.stride; };
+  auto row_of = [&](uint64_t k) { return in.mu_of ? (int64_t)in.mu_of[k] : (int64_t)k; };
+  // every item's terms before any work, as hafnian_complex plans them
+  const int T = std::max(o.threads, 1);
+  {
+    std::vector<uint64_t> sum(T, 0), bad(T, ~0ull);
+    std::vector<double> ops(T, 0.0);
+    std::atomic<int> next{0};
+    fock_parallel(L, T, [&](uint64_t a, uint64_t b) {
+      const int w = next.fetch_add(1);
+      for (uint64_t i = a; i < b; ++i) {
+        const uint64_t k = live[i];
+        const HafChoice c = haf_choose(list_of(k), in.n[k]);
+        if ((c.lay.H + 63) / 64 > kFockMaxChunks) bad[w] = std::min(bad[w], k);
+        sum[w] += c.lay.T;
+        ops[w] += (double)c.lay.T * haf_ops(c.lay.nwalk, in.n[k], true);
+      }
+    });
+    const uint64_t k = *std::min_element(bad.begin(), bad.end());
+    if (k != ~0ull) {
+      const HafChoice c = haf_choose(list_of(k), in.n[k]);
+      set_error(who + ": item k = " + std::to_string(k) + " has " + std::to_string(c.lay.T) +
+                " terms, more than 2^40 (2^24 wave-chunks of 64 lanes x 2^10 steps)");
+      return SUP_EUNSUPPORTED;
+    }
+    double osum = 0.0;
+    for (int w = 0; w < T; ++w) hi.terms += sum[w], osum += ops[w];
+    hi.ops = hi.terms ? osum / (double)hi.terms : 0.0;
+  }
+  uint64_t slab_max = ~0ull;
+  if (const char* e = std::getenv("SUP_HAFNIAN_SLAB")) {
+    const long long v = std::atoll(e);
+    if (v > 0) slab_max = (uint64_t)v;
+  }
+  int G = 1;
+  if (!on_cpu) {
+    int ndev = 0;
+    int rc = device_count(&ndev);
+    if (rc) return rc;
+    if (ndev == 0) {
+      set_error("no HIP device available (" + who + " has no CPU fallback; on_cpu = 1 runs host threads)");
+      return SUP_ENODEV;
+    }
+    if (o.device_id < 0 || o.device_id >= ndev) {
+      set_error(who + ": device_id out of range");
+      return SUP_EINVAL;
+    }
+    G = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::max(1, std::min(o.gpu_num, ndev - o.device_id)), L));
+  }
+  // one coefficient row per distinct order of the call: row n holds
+  // 1 / (j! (n - 2j)!), j <= n / 2, hafnian_complex's values
+  double fact[SUP_MAX_N + 1];
+  fact[0] = 1.0;
+  for (int i = 1; i <= SUP_MAX_N; ++i) fact[i] = fact[i - 1] * (double)i;
+  std::vector<double> coef;
+  uint32_t coef_at[SUP_MAX_N + 1];
+  {
+    bool seen[SUP_MAX_N + 1] = {false};
+    for (uint64_t i = 0; i < L; ++i) seen[in.n[live[i]]] = true;
+    for (int n = 1; n <= SUP_MAX_N; ++n) {
+      coef_at[n] = (uint32_t)coef.size();
+      if (seen[n])
+        for (int j = 0; j <= n / 2; ++j) coef.push_back(1.0 / (fact[j] * fact[n - 2 * j]));
+    }
+  }
+  std::vector<int> drc(G, SUP_OK), dgrid(G, 0);
+  std::vector<double> dms(G, 0.0);
+  std::vector<std::string> derr(G);
+  // live items [a, b) in slabs under hafnian_complex's caps; orders mix freely
+  auto work = [&](int g) {
+    const uint64_t a = L * (uint64_t)g / (uint64_t)G, b = L * (uint64_t)(g + 1) / (uint64_t)G;
+    try {
+      std::vector<double> res;
+      for (uint64_t i = a; i < b && !drc[g];) {
+        HafSlab S;
+        S.each = true;
+        S.loop = true;
+        S.coef = coef;
+        S.div = 1.0;
+        HafProgs progs;
+        size_t bytes = 0;
+        const uint64_t i0 = i;
+        int64_t lo = row_of(live[i]), hi_row = lo;
+        for (; i < b && i - i0 < slab_max; ++i) {
+          const uint64_t k = live[i];
+          const HafChoice c = haf_choose(list_of(k), in.n[k]);
+          const size_t add = haf_bytes(c, 16);
+          const uint64_t chunks = (c.lay.H + 63) / 64;
+          if (i > i0 && (bytes + add > kHafSlabCapBytes || S.chunks.size() + chunks > 0x7fffffffull)) break;
+          const int64_t row = row_of(k);
+          haf_append(S, hin, c, progs, on_cpu, in.mu + 2 * (uint64_t)in.M * (uint64_t)row,
+                     (uint32_t)in.n[k] | coef_at[in.n[k]] << 8);
+          S.mu_row.push_back((int32_t)row);
+          lo = std::min(lo, row), hi_row = std::max(hi_row, row);
+          bytes += add;
+        }
+        // the device takes rows [lo, hi_row] of mu alone
+        S.mu_lo = lo, S.mu_rows = hi_row - lo + 1;
+        for (int32_t& r : S.mu_row) r -= (int32_t)lo;
+        res.assign(2 * (i - i0), 0.0);
+        if (on_cpu) {
+          haf_cpu(S, std::max(o.threads, 1), res.data());
+        } else {
+          double ms = 0.0;
+          drc[g] = run_hafnian(o.device_id + g, S, hin, res.data(), &ms, &dgrid[g]);
+          if (drc[g]) derr[g] = last_error();
+          dms[g] += ms;
+        }
+        if (!drc[g])
+          for (uint64_t q = i0; q < i; ++q) out[2 * live[q]] = res[2 * (q - i0)], out[2 * live[q] + 1] = res[2 * (q - i0) + 1];
       }
     } catch (const std::bad_alloc&) {
       derr[g] = "out of host memory for a slab's tables and partials";

@@ -263,6 +263,14 @@ hipError_t launch_haf_prepare(const double* A, int M, const double* mu, const in
 // out[2k], out[2k + 1] = 2 x fock_fold over matrix k's partials, divided by div.
 hipError_t launch_haf_fold(const double* parts, const HafMat* mats, uint64_t K, double div, double* out,
                            hipStream_t s);
+// The ragged loop-hafnian batch (walk_lhafe.hip): the same queue with an order
+// and a coefficient row per matrix (HafMat::ord; p.coef = the pool of rows, p.n
+// unused), and a prepare that reads row mu_row[k] of mus (M complex each) for
+// matrix k.  The fold is launch_haf_fold with div = 1.
+hipError_t launch_lhafe(const HafParams& p, int grid, hipStream_t s);
+hipError_t lhafe_occupancy(int* blocks_per_cu);
+hipError_t launch_lhafe_prepare(const double* A, int M, const double* mus, const int32_t* mu_row, const int32_t* grp,
+                                const HafMat* mats, uint64_t K, double* tabs, hipStream_t s);
 
 // Fixed-order pairwise reduction of `count` doubles into *out (64-way passes,
 // zero padded; mirrored by oracle/oracle.c orc_pairwise_reduce).  `scratch`

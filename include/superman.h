@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SUP_ABI_VERSION 26  /* 26: sup_loop_hafnian_complex_each, sup_gbs_sample; 25: sup_torontonian_table, sup_loop_torontonian_table, sup_mobius_subsets, SUP_TORONTONIAN_TABLE_MAX_N; 24: sup_loop_torontonian, sup_loop_torontonian_range, sup_loop_torontonian_plan, sup_ltor_exp, sup_ltor_exp_device, SUP_LOOP_TORONTONIAN_MAX_DEVICE_N; 23: sup_hafnian_complex_exact; 22: sup_torontonian, sup_torontonian_range, sup_torontonian_plan, SUP_TORONTONIAN_MAX_DEVICE_N; 21: sup_hafnian_complex_pt, sup_loop_hafnian_complex_pt, sup_hafnian_complex_pt_range, sup_hafnian_complex_pt_plan, SUP_HAFNIAN_PT_MAX_DEVICE_N; 20: sup_hafnian_complex, sup_loop_hafnian_complex, sup_hafnian_complex_plan; 19: sup_perman_complex_exact, sup_perman_complex_exact_range, SUP_CPLX_EXACT_MAX_DEVICE_N; 18: sup_perman_complex_quad, sup_perman_complex_quad_range, SUP_CPLX_QUAD_MAX_DEVICE_N; 17:sup_perman_complex_fock_minors, sup_perman_complex_fock_minors_plan, sup_boson_sample_fock; 16: sup_plan_census; 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
+#define SUP_ABI_VERSION 27  /* 27: sup_loop_hafnian_table, sup_loop_hafnian_table_plan, SUP_LHAF_TABLE_MAX_ENTRIES; 26: sup_loop_hafnian_complex_each, sup_gbs_sample; 25: sup_torontonian_table, sup_loop_torontonian_table, sup_mobius_subsets, SUP_TORONTONIAN_TABLE_MAX_N; 24: sup_loop_torontonian, sup_loop_torontonian_range, sup_loop_torontonian_plan, sup_ltor_exp, sup_ltor_exp_device, SUP_LOOP_TORONTONIAN_MAX_DEVICE_N; 23: sup_hafnian_complex_exact; 22: sup_torontonian, sup_torontonian_range, sup_torontonian_plan, SUP_TORONTONIAN_MAX_DEVICE_N; 21: sup_hafnian_complex_pt, sup_loop_hafnian_complex_pt, sup_hafnian_complex_pt_range, sup_hafnian_complex_pt_plan, SUP_HAFNIAN_PT_MAX_DEVICE_N; 20: sup_hafnian_complex, sup_loop_hafnian_complex, sup_hafnian_complex_plan; 19: sup_perman_complex_exact, sup_perman_complex_exact_range, SUP_CPLX_EXACT_MAX_DEVICE_N; 18: sup_perman_complex_quad, sup_perman_complex_quad_range, SUP_CPLX_QUAD_MAX_DEVICE_N; 17:sup_perman_complex_fock_minors, sup_perman_complex_fock_minors_plan, sup_boson_sample_fock; 16: sup_plan_census; 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SUP_OK            0
@@ -786,6 +786,48 @@ int sup_gbs_sample(const double* B, int M,
                    const double* zeta, const double* het, /* nsamples x M complex each */
                    int cutoff, uint64_t nsamples, uint64_t sample0, uint64_t seed,
                    const sup_opts* o, int on_cpu, int32_t* out /* nsamples x M */, sup_stats* st);
+
+/* Loop-hafnian tables (ABI 27): every Fock amplitude up to a cutoff from one
+ * recurrence instead of one walk per pattern (lhaftab.hip, lhaf_table.cpp,
+ * lhaftab.hpp).  A is M x M complex, symmetric bit for bit, its
+ * diagonal counting pairs of copies of one mode; mu holds M complex loop
+ * weights on self-loops only (sup_loop_hafnian_complex's convention), NULL
+ * meaning zero: the plain hafnian table, whose entries of odd photon total are
+ * zero.  dims[i] = d_i in [1, 65] and n_i in [0, d_i).  With
+ *   t(n) = lhaf(A gathered with n_i copies of i, mu) / sqrt(prod n_i!)
+ * out holds t as (re, im) pairs at index x = sum_i n_i prod_{k<i} d_k (mode 0
+ * fastest): 2 prod d_i doubles.  out[0] = 1 + 0i exactly.  For x > 0, with p the
+ * highest occupied mode and m = n - e_p,
+ *   t(n) = [ mu_p t(m) + sum_{j <= p, m_j > 0} sqrt(m_j) A_pj t(m - e_j) ] / sqrt(n_p)
+ * j ascending, every complex multiply-add one fixed sequence of fmas per part,
+ * sqrt(k) and 1 / sqrt(k) from two host-made tables (lhaftab.hpp states each
+ * operation).  Row p of A is read up to column p.  An entry is a function of
+ * earlier entries only, so the device (one kernel for the prefix that fits a
+ * work-group's LDS, then one launch per slab n_p = c of each further mode p) and
+ * on_cpu = 1 (host threads, slab by slab) give the same bits, whatever the
+ * launch shape or thread count; a non-finite value reaches exactly the entries
+ * whose recurrence reads it.  SUP_LHAF_TABLE_LOW=E (read per call, 1 <= E <=
+ * 4096) makes the first kernel take at most E entries; the bits do not change.
+ * Errors, all before any device work: null A, dims or out, M outside [1, 64], a
+ * d_i outside [1, 65], an asymmetric pair, o->gpu_num > 1 (a table is one
+ * device's: o->device_id), a bad SUP_LHAF_TABLE_LOW: SUP_EINVAL; prod d_i above
+ * SUP_LHAF_TABLE_MAX_ENTRIES on either path: SUP_EUNSUPPORTED; no device with
+ * on_cpu = 0: SUP_ENODEV (no CPU fallback).  A table above 256 MiB is given
+ * back to the device after the call.
+ * st: leaves = 1, gray_steps = visited_steps = prod d_i, kernel_ms, grid = the
+ * work-groups of the largest launch, devices_used = 1 (0 with on_cpu),
+ * est_ops_per_step = the fp64 operations per entry (an fma counts once; the
+ * plan entry's figure), partials[0] = the kernel launches. */
+#define SUP_LHAF_TABLE_MAX_ENTRIES (1ull << 27)   /* 2 GiB of complex results, as ABI 25's cap */
+int sup_loop_hafnian_table(const double* A, int M, const double* mu /* NULL: hafnian table */,
+                           const int32_t* dims, const sup_opts* o, int on_cpu,
+                           double* out /* 2 * prod dims */, sup_stats* st);
+/* Host only: prod d_i (saturating at 2^64 - 1), the kernel launches of the
+ * device path (under SUP_LHAF_TABLE_LOW as set) and the operations per entry
+ * (0 when the product saturated).  Any output may be NULL.  Errors: null dims,
+ * M outside [1, 64], a d_i outside [1, 65], a bad SUP_LHAF_TABLE_LOW: SUP_EINVAL. */
+int sup_loop_hafnian_table_plan(const int32_t* dims, int M, uint64_t* entries, uint64_t* launches,
+                                double* ops_per_entry);
 
 /* Exact hafnians and loop hafnians of Gaussian-integer matrices (ABI 23): the
  * integer truth the floating hafnian entries are judged against, and exact

@@ -32,7 +32,9 @@ __all__ = [
            "torontonian_table", "loop_torontonian_table", "subset_mobius", "TORONTONIAN_TABLE_MAX_N",
            "MOBIUS_TILE_BITS", "MOBIUS_PASS_BITS", "threshold_detection_distribution", "threshold_detection_sample",
            "loop_hafnian_each", "gbs_pure_state", "pnr_detection_prob", "pnr_detection_probs", "gbs_sample",
-           "gbs_sample_chain",
+           "gbs_sample_chain", "loop_hafnian_table", "loop_hafnian_table_plan", "LHAF_TABLE_MAX_ENTRIES",
+           "gbs_state_vector", "gbs_density_matrix", "pnr_detection_distribution",
+           "pnr_detection_sample",
            "perman_complex_fock_minors_plan","perman_complex_minors", "perman_complex_minors_submatrices", "perman_complex_minors_range", "boson_sample", "read_mtx_complex", "partial", "perman_shard", "plan_info", "plan_census", "CENSUS_CLASSES", "plan_key", "prepare", "read_matrix", "read_mtx", "sort_order",
     "skip_order", "compress", "decompose", "perman_reduced", "approx", "grid_graph", "ALGOS_APPROX",
     "nw_start", "device_count", "rccl_devices", "layout", "ShardCall", "SupError", "ALGOS_DENSE", "ALGOS_SPARSE",
@@ -1447,6 +1449,149 @@ def pnr_detection_probs(mu, cov, patterns, hbar: float = 2.0, **kw):
 def pnr_detection_prob(mu, cov, pattern, hbar: float = 2.0, **kw):
     """The probability of one photon-number pattern (``pnr_detection_probs``)."""
     return pnr_detection_probs(mu, cov, np.asarray(pattern).reshape(-1), hbar=hbar, **kw)
+
+
+# include/superman.h SUP_LHAF_TABLE_MAX_ENTRIES: the most entries a loop-hafnian
+# table takes (2^27 complex values = 2 GiB), on the device and on host threads
+LHAF_TABLE_MAX_ENTRIES = 1 << 27
+
+
+def _lhaf_dims(dims, M=None):
+    d = np.asarray(dims)
+    if d.ndim == 0 and M is not None:  # a cutoff: photon numbers 0 .. cutoff on every mode
+        d = np.full(M, int(d) + 1)
+    d = d.reshape(-1)
+    if d.size < 1 or not np.issubdtype(d.dtype, np.integer) or d.min() < -2**31 or d.max() >= 2**31:
+        raise ValueError(f"dims must hold at least one 32-bit integer, got {dims}")
+    if M is not None and d.size != M:
+        raise ValueError(f"dims must hold one size per mode, M = {M}; got {d.size}")
+    return np.ascontiguousarray(d, dtype=np.int32)
+
+
+def loop_hafnian_table(A, mu, dims, cpu: bool = False, threads: int = 16, device_id: int = 0,
+                       return_stats: bool = False):
+    """Every normalised loop hafnian of A up to per-mode cutoffs from ONE
+    recurrence (sup_loop_hafnian_table): a complex array of shape
+    ``tuple(dims)`` with ``t[n_0, .., n_{M-1}] = lhaf(A gathered with n_i copies
+    of i, mu) / sqrt(prod n_i!)`` for n_i < dims[i], the diagonal of A counting
+    pairs of copies of one mode and ``mu`` on self-loops only.  ``mu=None``
+    gives the hafnian table (odd photon totals are 0).  ``t[0, .., 0]`` is
+    exactly 1.  The array is the Fortran-order view of the C buffer (mode 0
+    fastest), no copy.  One device or (cpu=True) the host twin, bit-identical;
+    prod dims <= ``LHAF_TABLE_MAX_ENTRIES``."""
+    a = np.ascontiguousarray(np.asarray(A, dtype=np.complex128))
+    if a.ndim != 2 or a.shape[0] != a.shape[1] or a.shape[0] < 1:
+        raise ValueError(f"expected a non-empty square matrix A, got shape {a.shape}")
+    M = a.shape[0]
+    d = _lhaf_dims(dims, M)
+    m = None
+    if mu is not None:
+        m = np.ascontiguousarray(np.asarray(mu, dtype=np.complex128))
+        if m.shape != (M,):
+            raise ValueError(f"mu must have shape [{M}], got {m.shape}")
+    total = 1
+    for v in d.tolist():
+        total *= max(v, 0)
+    # a refused call writes nothing: no buffer of the full size for it
+    ok = M <= 64 and d.min() >= 1 and d.max() <= 65 and total <= LHAF_TABLE_MAX_ENTRIES
+    out, st = np.zeros(total if ok else 1, np.complex128), SupStats()
+    op = _opts(gpu_num=1, device_id=device_id, threads=threads)
+    rc = _lib.load().sup_loop_hafnian_table(a.ctypes.data, M, None if m is None else m.ctypes.data, d.ctypes.data,
+                                            C.byref(op), int(bool(cpu)), out.ctypes.data, C.byref(st))
+    _lib.check(rc, "loop_hafnian_table")
+    t = out.reshape(tuple(d.tolist()), order="F")
+    if not return_stats:
+        return t
+    s = st.as_dict()
+    s["launches"] = int(st.partials[0])
+    return t, s
+
+
+def loop_hafnian_table_plan(dims):
+    """``(entries, launches, ops_per_entry)`` of ``loop_hafnian_table`` at
+    ``dims`` (sup_loop_hafnian_table_plan, host only): prod dims, the kernel
+    launches of the device path and the fp64 operations per entry."""
+    d = _lhaf_dims(dims)
+    e, l, ops = C.c_uint64(0), C.c_uint64(0), C.c_double(0.0)
+    _lib.check(_lib.load().sup_loop_hafnian_table_plan(d.ctypes.data, d.size, C.byref(e), C.byref(l), C.byref(ops)),
+               "loop_hafnian_table_plan")
+    return int(e.value), int(l.value), float(ops.value)
+
+
+def gbs_state_vector(mu, cov, dims_or_cutoff, hbar: float = 2.0, **kw):
+    """The Fock amplitudes ``psi[n_0, .., n_{M-1}]``, n_i < dims[i] (or <= an
+    integer cutoff), of the pure Gaussian state ``mu`` (or None), ``cov`` (xxpp
+    ordering): sqrt(p0) times ``loop_hafnian_table`` of ``gbs_pure_state``'s B
+    and zeta, up to one global phase.  Mixed states raise ValueError as
+    ``gbs_pure_state`` does.  ``kw`` goes to the table call (cpu, threads,
+    device_id)."""
+    B, zeta, p0 = gbs_pure_state(mu, cov, hbar)
+    d = _lhaf_dims(dims_or_cutoff, B.shape[0])
+    return np.sqrt(p0) * loop_hafnian_table(B, None if mu is None else zeta, d, **kw)
+
+
+def gbs_density_matrix(mu, cov, dims_or_cutoff, hbar: float = 2.0, **kw):
+    """The density matrix of ANY Gaussian state in the Fock basis up to the
+    cutoffs: an array of 2M axes of shape dims + dims, ``rho[n_0, .., n_{M-1},
+    m_0, .., m_{M-1}] = <n| rho |m>``, from one ``loop_hafnian_table`` of the
+    2M x 2M Abar and conj(gamma) of ``pnr_detection_probs`` at dims + dims, times
+    p0.  A pure state gives psi psi^dagger of ``gbs_state_vector``.  ValueError
+    when prod dims^2 exceeds ``LHAF_TABLE_MAX_ENTRIES``."""
+    O, gamma, pre = _threshold_setup(mu, cov, hbar)
+    M = O.shape[0] // 2
+    d = _lhaf_dims(dims_or_cutoff, M)
+    if d.min() >= 1:
+        D = 1
+        for v in d.tolist():
+            D *= v
+        if D * D > LHAF_TABLE_MAX_ENTRIES:
+            raise ValueError(f"a density matrix at dims {tuple(d.tolist())} has {D}^2 = {D * D} entries, more than "
+                             f"LHAF_TABLE_MAX_ENTRIES = {LHAF_TABLE_MAX_ENTRIES}")
+    Abar = np.concatenate([O[M:], O[:M]])
+    Abar = np.ascontiguousarray((Abar + Abar.T) / 2.0)
+    t = loop_hafnian_table(Abar, None if gamma is None else np.conj(gamma), np.concatenate([d, d]), **kw)
+    # Abar's second block is gbs_pure_state's B: its axes are the ket's
+    return pre * np.transpose(t, list(range(M, 2 * M)) + list(range(M)))
+
+
+def pnr_detection_distribution(mu, cov, dims_or_cutoff, modes=None, hbar: float = 2.0, **kw):
+    """The joint photon-number distribution ``p[n_0, .., n_{k-1}]``, n_i <
+    dims[i] (or <= an integer cutoff), of the listed modes (default: all M; the
+    others are traced out first, as ``threshold_detection_distribution`` does)
+    on photon-number-resolving detectors.  A pure state takes |psi|^2 of
+    ``gbs_state_vector``; any other state the diagonal of
+    ``gbs_density_matrix``.  1 - p.sum() is the mass above the cutoffs."""
+    mu_r, cov_r = _threshold_reduce(mu, cov, modes)
+    try:
+        psi = gbs_state_vector(mu_r, cov_r, dims_or_cutoff, hbar=hbar, **kw)
+    except ValueError as e:
+        if "not pure" not in str(e):
+            raise
+        psi = None
+    if psi is not None:
+        return psi.real * psi.real + psi.imag * psi.imag
+    rho = gbs_density_matrix(mu_r, cov_r, dims_or_cutoff, hbar=hbar, **kw)
+    k = rho.ndim // 2
+    D = int(np.prod(rho.shape[:k]))
+    return np.ascontiguousarray(rho.reshape(D, D, order="F").diagonal().real).reshape(rho.shape[:k], order="F")
+
+
+def pnr_detection_sample(mu, cov, nsamples: int, seed: int, dims_or_cutoff, return_missing: bool = False, modes=None,
+                         hbar: float = 2.0, **kw):
+    """``nsamples`` exact photon-number patterns (int32 [nsamples, k]) from
+    ``pnr_detection_distribution`` renormalised over the table, by the inverse
+    CDF in the C buffer's order (mode 0 fastest): negative roundings count as 0,
+    and the uniform numbers are ``numpy.random.default_rng(seed)``'s.  The
+    samples are a function of the table's bits: the same on the device and with
+    ``cpu=True``.  ``return_missing=True`` also gives 1 - sum p, the mass above
+    the cutoffs that the renormalisation spreads."""
+    p = pnr_detection_distribution(mu, cov, dims_or_cutoff, modes=modes, hbar=hbar, **kw)
+    flat = np.clip(p.reshape(-1, order="F"), 0.0, None)
+    cdf = np.cumsum(flat)
+    u = np.random.default_rng(seed).random(int(nsamples)) * cdf[-1]
+    idx = np.minimum(np.searchsorted(cdf, u, side="right"), flat.shape[0] - 1)
+    pat = np.stack(np.unravel_index(idx, p.shape, order="F"), axis=1).astype(np.int32)
+    return (pat, float(1.0 - flat.sum())) if return_missing else pat
 
 
 def gbs_sample_chain(B, zeta, het, seed: int, cutoff: int = 8, sample0: int = 0, gpu_num: int = 1, device_id: int = 0,

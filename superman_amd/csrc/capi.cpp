@@ -11,6 +11,7 @@
 #include "hafnian_pt.hpp"
 #include "loop_torontonian.hpp"
 #include "torontonian.hpp"
+#include "lhaf_table.hpp"
 #include "torontonian_table.hpp"
 
 using namespace sup;
@@ -714,6 +715,35 @@ int sup_gbs_sample(const double* B, int M, const double* zeta, const double* het
     st->partials[2] = (double)gi.failed;  // samples whose weights summed to zero or to a non-finite value
   }
   return SUP_OK;
+}
+
+int sup_loop_hafnian_table(const double* A, int M, const double* mu, const int32_t* dims, const sup_opts* o_in,
+                           int on_cpu, double* out, sup_stats* st) {
+  auto t0 = std::chrono::steady_clock::now();
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  LhafTabInfo ti;
+  if (int rc = loop_hafnian_table(A, M, mu, dims, o, on_cpu != 0, out, &ti)) return rc;
+  if (st) {
+    std::memset(st, 0, sizeof(*st));
+    st->kernel_ms = ti.kernel_ms;
+    st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    st->gray_steps = ti.entries;
+    st->visited_steps = ti.entries;
+    st->devices_used = ti.devices;
+    st->grid = ti.grid;
+    st->walk_kind = (int)kWalkDense;
+    st->leaves = 1;
+    st->est_ops_per_step = ti.ops;
+    st->partials[0] = (double)ti.launches;  // kernel launches of the device path
+  }
+  return SUP_OK;
+}
+
+int sup_loop_hafnian_table_plan(const int32_t* dims, int M, uint64_t* entries, uint64_t* launches,
+                                double* ops_per_entry) {
+  return loop_hafnian_table_plan(dims, M, entries, launches, ops_per_entry);
 }
 
 int sup_hafnian_complex_exact(const double* A, int M, const double* mu, const int32_t* idx, int n, uint64_t count,

@@ -5,6 +5,7 @@
 #include "engine.hpp"
 #include "hafnian_exact.hpp"
 #include "hafnian_pt.hpp"
+#include "lhaf_table.hpp"
 #include "loop_torontonian.hpp"
 #include "torontonian.hpp"
 #include "torontonian_table.hpp"
@@ -1950,6 +1951,46 @@ int run_ltor_exp(int dev, const double* x, uint64_t count, double* out) {
   SUP_HIP(hipMemcpyAsync(out, c->d_cbout, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, s));
   double ms = 0.0;
   return timed_sync(c, &ms);
+}
+
+// Loop-hafnian table (lhaftab.hip): A, zeta and the two root tables go up, the
+// low kernel and the slab launches follow on the context's stream, and one
+// download brings the 2 * entries doubles into out.  The table lives in d_cbout
+// and follows release_table's rule.
+int run_lhaf_table(int dev, const double* A, int M, const double* zeta, const int32_t* dims, uint64_t entries, uint32_t low,
+                   double* out, double* kernel_ms, int* grid_out, uint64_t* launches) {
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (grid_out) *grid_out = 0;
+  if (launches) *launches = 0;
+  if (!A || !zeta || !dims || !out || M < 1 || M > kLhafTabMaxM || entries < 1 || entries > kLhafTabMaxEntries || low < 1 ||
+      low > kLhafLowTile) {
+    set_error("run_lhaf_table: bad request");
+    return SUP_EINVAL;
+  }
+  double roots[2 * kLhafTabMaxDim];
+  lhaf_roots(roots, roots + kLhafTabMaxDim);
+  const size_t a_doubles = (size_t)2 * M * M, z_doubles = (size_t)2 * M;
+  CtxGuard guard;
+  int rc = guard.open(dev, "device buffers");
+  if (rc) return rc;
+  DeviceCtx* c = guard.c;
+  if ((rc = ensure(c->d_cbU, c->cbU_cap, a_doubles + z_doubles + 2 * kLhafTabMaxDim))) return rc;
+  if ((rc = ensure(c->d_cbout, c->cbout_cap, (size_t)(2 * entries)))) return rc;
+  hipStream_t s = c->stream;
+  double* dz = c->d_cbU + a_doubles;
+  double* ds = dz + z_doubles;
+  SUP_HIP(hipMemcpyAsync(c->d_cbU, A, a_doubles * sizeof(double), hipMemcpyHostToDevice, s));
+  SUP_HIP(hipMemcpyAsync(dz, zeta, z_doubles * sizeof(double), hipMemcpyHostToDevice, s));
+  SUP_HIP(hipMemcpyAsync(ds, roots, sizeof(roots), hipMemcpyHostToDevice, s));
+  SUP_HIP(hipEventRecord(c->ev0, s));
+  SUP_ON_DEVICE(c->dev, "loop-hafnian table launch");
+  SUP_HIP(launch_lhaf_table(A, zeta, roots + kLhafTabMaxDim, dims, M, low, c->d_cbU, dz, ds, ds + kLhafTabMaxDim, c->d_cbout, s,
+                            launches, grid_out));
+  SUP_HIP(hipEventRecord(c->ev1, s));
+  SUP_HIP(hipMemcpyAsync(out, c->d_cbout, (size_t)(2 * entries) * sizeof(double), hipMemcpyDeviceToHost, s));
+  rc = timed_sync(c, kernel_ms);
+  release_table(c);
+  return rc;
 }
 
 }  // namespace sup

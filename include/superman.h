@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SUP_ABI_VERSION 27  /* 27: sup_loop_hafnian_table, sup_loop_hafnian_table_plan, SUP_LHAF_TABLE_MAX_ENTRIES; 26: sup_loop_hafnian_complex_each, sup_gbs_sample; 25: sup_torontonian_table, sup_loop_torontonian_table, sup_mobius_subsets, SUP_TORONTONIAN_TABLE_MAX_N; 24: sup_loop_torontonian, sup_loop_torontonian_range, sup_loop_torontonian_plan, sup_ltor_exp, sup_ltor_exp_device, SUP_LOOP_TORONTONIAN_MAX_DEVICE_N; 23: sup_hafnian_complex_exact; 22: sup_torontonian, sup_torontonian_range, sup_torontonian_plan, SUP_TORONTONIAN_MAX_DEVICE_N; 21: sup_hafnian_complex_pt, sup_loop_hafnian_complex_pt, sup_hafnian_complex_pt_range, sup_hafnian_complex_pt_plan, SUP_HAFNIAN_PT_MAX_DEVICE_N; 20: sup_hafnian_complex, sup_loop_hafnian_complex, sup_hafnian_complex_plan; 19: sup_perman_complex_exact, sup_perman_complex_exact_range, SUP_CPLX_EXACT_MAX_DEVICE_N; 18: sup_perman_complex_quad, sup_perman_complex_quad_range, SUP_CPLX_QUAD_MAX_DEVICE_N; 17:sup_perman_complex_fock_minors, sup_perman_complex_fock_minors_plan, sup_boson_sample_fock; 16: sup_plan_census; 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
+#define SUP_ABI_VERSION 28  /* 28: sup_loop_torontonian_each, sup_threshold_sample; 27: sup_loop_hafnian_table, sup_loop_hafnian_table_plan, SUP_LHAF_TABLE_MAX_ENTRIES; 26: sup_loop_hafnian_complex_each, sup_gbs_sample; 25: sup_torontonian_table, sup_loop_torontonian_table, sup_mobius_subsets, SUP_TORONTONIAN_TABLE_MAX_N; 24: sup_loop_torontonian, sup_loop_torontonian_range, sup_loop_torontonian_plan, sup_ltor_exp, sup_ltor_exp_device, SUP_LOOP_TORONTONIAN_MAX_DEVICE_N; 23: sup_hafnian_complex_exact; 22: sup_torontonian, sup_torontonian_range, sup_torontonian_plan, SUP_TORONTONIAN_MAX_DEVICE_N; 21: sup_hafnian_complex_pt, sup_loop_hafnian_complex_pt, sup_hafnian_complex_pt_range, sup_hafnian_complex_pt_plan, SUP_HAFNIAN_PT_MAX_DEVICE_N; 20: sup_hafnian_complex, sup_loop_hafnian_complex, sup_hafnian_complex_plan; 19: sup_perman_complex_exact, sup_perman_complex_exact_range, SUP_CPLX_EXACT_MAX_DEVICE_N; 18: sup_perman_complex_quad, sup_perman_complex_quad_range, SUP_CPLX_QUAD_MAX_DEVICE_N; 17:sup_perman_complex_fock_minors, sup_perman_complex_fock_minors_plan, sup_boson_sample_fock; 16: sup_plan_census; 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SUP_OK            0
@@ -1007,6 +1007,67 @@ int sup_loop_torontonian_plan(int n, uint64_t* subsets, double* est_ops);
  * count = 0 does nothing).  The two agree bit for bit. */
 double sup_ltor_exp(double x);
 int sup_ltor_exp_device(const double* x, uint64_t count, double* out, int device_id);
+
+/* Ragged loop torontonians with a displacement per item (ABI 28): the batch one
+ * chain-rule step of a threshold-detector sampler needs.  O as above; gamma
+ * holds ngamma rows of 2M complex; item k, k < count, is the loop torontonian
+ * of the list modes[k stride .. k stride + n[k]) with row gamma_of[k] of gamma
+ * (gamma_of NULL: row k), 0 <= n[k] <= 32 and stride >= max n[k] (entries past
+ * n[k] are not read).  Item k with n[k] >= 1 has the bits of
+ * sup_loop_torontonian(O, M, gamma + 4 M gamma_of[k], modes + stride k, n[k], 1, ..);
+ * an item with n[k] = 0 is exactly 1.0 and walks nothing.  The items of a call
+ * share slabs (by bytes, under 2^31 wave-chunks; SUP_LTOR_EACH_SLAB, read per
+ * call, caps the items of a slab): items of different order sit next to each
+ * other in one wave-chunk queue, and the kernel (walk_ltore, walk_ltor.hip)
+ * reads the order, the padded order, the chunk size and the place of the
+ * item's matrix per item.  o->gpu_num devices take contiguous
+ * ranges of the walking items.  Bit-identical on the device, on any device
+ * count, for any slab size and queue group and on host threads.  A pivot that
+ * is not positive makes that item NaN and no other.
+ * Errors, all before any device work: a null pointer (gamma_of alone may be
+ * NULL), M < 1, n[k] outside [0, 32], stride < n[k], gamma_of[k] (or k) outside
+ * [0, ngamma), a mode outside [0, M) or named twice in a list, a
+ * SUP_LTOR_EACH_SLAB that is no positive integer: SUP_EINVAL with a message
+ * naming the place; no device with on_cpu = 0: SUP_ENODEV (no CPU fallback).
+ * st: leaves = count, gray_steps = visited_steps = sum_k 2^n[k] over the items
+ * with n[k] >= 1, kernel_ms, wall_ms, devices_used, grid, est_ops_per_step =
+ * the census ltor_ops(n[k]) weighted by 2^n[k]. */
+int sup_loop_torontonian_each(const double* O, int M,
+                              const double* gamma, uint64_t ngamma, /* ngamma x 2M complex rows        */
+                              const int32_t* gamma_of,              /* count; NULL: item k uses row k  */
+                              const int32_t* modes, int stride,     /* count x stride, first n[k] used */
+                              const int32_t* n,                     /* count, each in [0, 32]          */
+                              uint64_t count, const sup_opts* o, int on_cpu, double* out, sup_stats* st);
+/* A threshold-detector Gaussian boson sampler for pure states (ABI 28):
+ * sup_gbs_sample's chain rule with click / no-click outcomes on the entry
+ * above (threshold_sample.cpp).  B, zeta, het, seed and sample0
+ * are sup_gbs_sample's.  One matrix O = [[0, B], [conj B, 0]] serves every step
+ * and sample.  For mode k = 0 .. M-1 of sample s, with C the modes below k that
+ * clicked, ascending,
+ *   z_i = zeta_i + sum_{j > k} B_ij conj(alpha_j), i <= k   (sup_gbs_sample's fmas)
+ *   gamma = (z, conj z), zero above k
+ *   w_0 = ltor(O, gamma, C),  w_1 = ltor(O, gamma, C + [k])
+ *         (a weight that is negative or -0 counts as +0)
+ *   u   = (w64(seed, sample0 + s, step k) >> 11) 2^-53
+ *   out[s][k] = the first c whose running sum of w exceeds u (w_0 + w_1); a
+ *         zero weight is never chosen
+ * and every step is one sup_loop_torontonian_each call of two items per sample
+ * of a batch.  When w_0 + w_1 is zero or not finite, or the list with k would
+ * pass 32 modes, that mode and every later one are -1.  weights (NULL, or
+ * nsamples x M x 2 doubles) receives (w_0, w_1) as used, zeros for the modes a
+ * failed sample did not reach.  Sample s depends on (B, zeta[s], het[s], seed,
+ * sample0 + s) only; the device and on_cpu = 1 draw identical samples.
+ * Errors: null B, M outside [1, 64], B not symmetric: SUP_EINVAL; then
+ * nsamples = 0 returns SUP_OK; a null zeta, het or out: SUP_EINVAL; no device
+ * with on_cpu = 0: SUP_ENODEV.
+ * st: as sup_gbs_sample's (kernel_ms summed over the steps, partials[0] / [1] =
+ * wall ms in the each-calls / in the host stage, partials[2] = samples that
+ * ended in -1). */
+int sup_threshold_sample(const double* B, int M,
+                         const double* zeta, const double* het, /* nsamples x M complex each */
+                         uint64_t nsamples, uint64_t sample0, uint64_t seed,
+                         const sup_opts* o, int on_cpu, int32_t* out /* nsamples x M */,
+                         double* weights /* NULL or nsamples x M x 2 */, sup_stats* st);
 
 /* Torontonian tables (ABI 25): every click pattern of one list of n distinct
  * modes from one walk.  f(z) depends on the selected positions only, so for

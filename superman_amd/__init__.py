@@ -32,7 +32,7 @@ __all__ = [
            "torontonian_table", "loop_torontonian_table", "subset_mobius", "TORONTONIAN_TABLE_MAX_N",
            "MOBIUS_TILE_BITS", "MOBIUS_PASS_BITS", "threshold_detection_distribution", "threshold_detection_sample",
            "loop_hafnian_each", "gbs_pure_state", "pnr_detection_prob", "pnr_detection_probs", "gbs_sample",
-           "gbs_sample_chain", "loop_hafnian_table", "loop_hafnian_table_plan", "LHAF_TABLE_MAX_ENTRIES",
+           "gbs_sample_chain", "loop_torontonian_each", "threshold_sample_chain", "threshold_sample", "loop_hafnian_table", "loop_hafnian_table_plan", "LHAF_TABLE_MAX_ENTRIES",
            "gbs_state_vector", "gbs_density_matrix", "pnr_detection_distribution",
            "pnr_detection_sample",
            "perman_complex_fock_minors_plan","perman_complex_minors", "perman_complex_minors_submatrices", "perman_complex_minors_range", "boson_sample", "read_mtx_complex", "partial", "perman_shard", "plan_info", "plan_census", "CENSUS_CLASSES", "plan_key", "prepare", "read_matrix", "read_mtx", "sort_order",
@@ -1648,7 +1648,15 @@ def gbs_sample(mu, cov, nsamples: int, seed: int, cutoff: int = 8, hbar: float =
     samples on the device and with ``cpu=True``; rows drawn in pieces with
     ``sample0`` equal the whole run's.  ``kw`` goes to ``gbs_sample_chain``."""
     B, zeta, _ = gbs_pure_state(mu, cov, hbar)
-    M = B.shape[0]
+    het = _gbs_heterodyne(mu, cov, B.shape[0], nsamples, seed, hbar, sample0)
+    return gbs_sample_chain(B, zeta, het, seed, cutoff=cutoff, sample0=int(sample0), **kw)
+
+
+def _gbs_heterodyne(mu, cov, M, nsamples, seed, hbar, sample0):
+    """Rows [sample0, sample0 + nsamples) of the heterodyne outcomes the chain
+    rule samplers condition on: ``numpy.random.default_rng(seed)
+    .standard_normal((sample0 + nsamples, 2M))`` times the Cholesky factor of
+    cov + (hbar / 2) I plus the mean, as complex amplitudes [nsamples, M]."""
     nsamples, sample0 = int(nsamples), int(sample0)
     if nsamples < 0 or sample0 < 0:
         raise ValueError("nsamples and sample0 must be >= 0")
@@ -1658,8 +1666,120 @@ def gbs_sample(mu, cov, nsamples: int, seed: int, cutoff: int = 8, hbar: float =
     xp = g @ L.T
     if mu is not None:
         xp = xp + np.asarray(mu, dtype=np.float64)[None, :]
-    het = (xp[:, :M] + 1j * xp[:, M:]) / np.sqrt(2.0 * float(hbar))
-    return gbs_sample_chain(B, zeta, het, seed, cutoff=cutoff, sample0=sample0, **kw)
+    return (xp[:, :M] + 1j * xp[:, M:]) / np.sqrt(2.0 * float(hbar))
+
+
+def loop_torontonian_each(O, gammas, lists, gamma_of=None, gpu_num: int = 1, device_id: int = 0, cpu: bool = False,
+                          threads: int = 16, return_stats: bool = False):
+    """The loop torontonians of ragged lists of distinct modes of one 2M x 2M
+    Hermitian matrix O, each with its own displacement
+    (sup_loop_torontonian_each): item k is ``loop_torontonian_batch(O,
+    gammas[gamma_of[k]], lists[k])`` (``gamma_of=None``: row k), bit for bit.
+    ``gammas`` has shape [ngamma, 2M] (or [2M]: one row).  The lists may differ
+    in length (0..32); an empty list gives exactly 1.  One call is one queue on
+    the device (walk_ltore in walk_ltor.hip) whatever the orders.  float64 array
+    of shape [count]."""
+    o = _tor_matrix(O)
+    g = np.ascontiguousarray(np.asarray(gammas, dtype=np.complex128))
+    if g.ndim == 1:
+        g = g[None, :]
+    if g.ndim != 2 or g.shape[1] != o.shape[0] or g.shape[0] < 1:
+        raise ValueError(f"gammas must have shape [ngamma, {o.shape[0]}] with ngamma >= 1, got {g.shape}")
+    rows = [np.asarray(l).reshape(-1) for l in lists]
+    count = len(rows)
+    n32 = np.array([r.size for r in rows] + [0], dtype=np.int64)
+    flat = np.concatenate([r for r in rows if r.size]) if n32.sum() else np.zeros(0, np.int64)
+    if flat.size and not np.issubdtype(flat.dtype, np.integer):
+        raise ValueError(f"lists must hold integers, got dtype {flat.dtype}")
+    if flat.size and (flat.min() < -2**31 or flat.max() >= 2**31):
+        raise ValueError("lists hold a mode outside the 32-bit range")
+    stride = max(int(n32.max()), 1)
+    idx = np.zeros((max(count, 1), stride), np.int32)
+    if flat.size:  # row k's entries at idx[k, :n[k]]
+        first = np.cumsum(n32[:count]) - n32[:count]
+        idx[np.repeat(np.arange(count), n32[:count]), np.arange(flat.size) - np.repeat(first, n32[:count])] = flat
+    n32 = np.ascontiguousarray(n32[:max(count, 1)], dtype=np.int32)
+    of = None
+    if gamma_of is not None:
+        ofa = np.asarray(gamma_of)
+        if ofa.shape != (count,) or (count and not np.issubdtype(ofa.dtype, np.integer)):
+            raise ValueError(f"gamma_of must hold one integer per list, got shape {ofa.shape}")
+        if count and (ofa.min() < -2**31 or ofa.max() >= 2**31):
+            raise ValueError("gamma_of holds a row outside the 32-bit range")
+        of = np.ascontiguousarray(ofa, dtype=np.int32) if count else np.zeros(1, np.int32)
+    lib = _lib.load()
+    op = _opts(gpu_num=gpu_num, device_id=device_id, threads=threads)
+    out, st = np.zeros(max(count, 1)), SupStats()
+    rc = lib.sup_loop_torontonian_each(o.ctypes.data, o.shape[0] // 2, g.ctypes.data, g.shape[0],
+                                       None if of is None else of.ctypes.data, idx.ctypes.data, stride, n32.ctypes.data,
+                                       count, C.byref(op), int(bool(cpu)), out.ctypes.data, C.byref(st))
+    _lib.check(rc, "loop_torontonian_each")
+    v = out[:count].copy()
+    return (v, st.as_dict()) if return_stats else v
+
+
+def threshold_sample_chain(B, zeta, het, seed: int, sample0: int = 0, return_weights: bool = False, gpu_num: int = 1,
+                           device_id: int = 0, cpu: bool = False, threads: int = 16, return_stats: bool = False):
+    """The deterministic part of the threshold-detector sampler
+    (sup_threshold_sample): the chain rule over the modes for the pure state
+    ``B`` (M x M symmetric), ``zeta`` ([nsamples, M], or [M] for every sample)
+    and the heterodyne outcomes ``het`` ([nsamples, M] complex).  Every mode step
+    is one ragged loop torontonian call of two items per sample of a batch: the
+    clicks so far without and with the mode.  Row s depends on (B, zeta[s],
+    het[s], seed, sample0 + s) only.  int32 [nsamples, M] of 0 / 1; -1 from the
+    mode on at which a sample's two weights summed to zero or to a non-finite
+    value or its list would pass 32 modes.  ``return_weights=True`` adds the
+    float64 array [nsamples, M, 2] of (w_0, w_1) as used; ``return_stats=True``
+    the statistics, last."""
+    b = np.ascontiguousarray(np.asarray(B, dtype=np.complex128))
+    if b.ndim != 2 or b.shape[0] != b.shape[1] or b.shape[0] < 1:
+        raise ValueError(f"expected a non-empty square matrix B, got shape {b.shape}")
+    M = b.shape[0]
+    h = np.ascontiguousarray(np.asarray(het, dtype=np.complex128))
+    if h.ndim != 2 or h.shape[1] != M:
+        raise ValueError(f"het must have shape [nsamples, {M}], got {h.shape}")
+    ns = h.shape[0]
+    z = np.asarray(zeta, dtype=np.complex128)
+    if z.shape == (M,):
+        z = np.broadcast_to(z, (ns, M))
+    if z.shape != (ns, M):
+        raise ValueError(f"zeta must have shape [{M}] or [{ns}, {M}], got {z.shape}")
+    z = np.ascontiguousarray(z)
+    if sample0 < 0:
+        raise ValueError("sample0 must be >= 0")
+    lib = _lib.load()
+    o = _opts(gpu_num=gpu_num, device_id=device_id, threads=threads)
+    out, st = np.zeros((max(ns, 1), M), np.int32), SupStats()
+    w = np.zeros((max(ns, 1), M, 2)) if return_weights else None
+    hp = h.ctypes.data if ns else out.ctypes.data
+    zp = z.ctypes.data if ns else out.ctypes.data
+    _lib.check(lib.sup_threshold_sample(b.ctypes.data, M, zp, hp, ns, int(sample0), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                        C.byref(o), int(bool(cpu)), out.ctypes.data,
+                                        None if w is None else w.ctypes.data, C.byref(st)), "threshold_sample")
+    res = [out[:ns].copy()]
+    if return_weights:
+        res.append(w[:ns].copy())
+    if return_stats:
+        d = st.as_dict()
+        d["each_ms"], d["host_ms"], d["failed"] = float(st.partials[0]), float(st.partials[1]), int(st.partials[2])
+        res.append(d)
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+def threshold_sample(mu, cov, nsamples: int, seed: int, hbar: float = 2.0, sample0: int = 0, **kw):
+    """``nsamples`` click patterns (int32 [nsamples, M] of 0 / 1) of the pure
+    Gaussian state ``mu`` (or None), ``cov`` (xxpp ordering) on threshold
+    detectors, by the chain rule of Bulmer et al. 2022 with loop torontonians
+    for the two outcomes of a mode: exact, and not bounded by a table's 28
+    modes (a sample may click on 32 modes at most).  The heterodyne outcomes
+    are ``gbs_sample``'s for the same seed; the rest is
+    ``threshold_sample_chain``.  Mixed states raise ValueError
+    (``gbs_pure_state``).  The same samples on the device and with
+    ``cpu=True``; rows drawn in pieces with ``sample0`` equal the whole run's.
+    ``kw`` goes to ``threshold_sample_chain``."""
+    B, zeta, _ = gbs_pure_state(mu, cov, hbar)
+    het = _gbs_heterodyne(mu, cov, B.shape[0], nsamples, seed, hbar, sample0)
+    return threshold_sample_chain(B, zeta, het, seed, sample0=int(sample0), **kw)
 
 
 def partial(mat, start: int, end: int, kernel: str = "dense", gpu_num: int = 1, device_id: int = 0,

@@ -923,6 +923,58 @@ int sup_loop_torontonian_plan(int n, uint64_t* subsets, double* est_ops) {
   return loop_torontonian_plan(n, subsets, est_ops);
 }
 
+int sup_loop_torontonian_each(const double* O, int M, const double* gamma, uint64_t ngamma, const int32_t* gamma_of,
+                              const int32_t* modes, int stride, const int32_t* n, uint64_t count, const sup_opts* o_in,
+                              int on_cpu, double* out, sup_stats* st) {
+  auto t0 = std::chrono::steady_clock::now();
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  LtorEachIn in;
+  in.O = O, in.M = M, in.gamma = gamma, in.ngamma = ngamma, in.gamma_of = gamma_of, in.modes = modes, in.stride = stride;
+  in.n = n;
+  TorInfo ti;
+  if (int rc = loop_torontonian_each(in, count, o, on_cpu != 0, out, &ti)) return rc;
+  if (st) {
+    std::memset(st, 0, sizeof(*st));
+    st->kernel_ms = ti.kernel_ms;
+    st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    st->gray_steps = ti.subsets;
+    st->visited_steps = ti.subsets;
+    st->devices_used = ti.devices;
+    st->grid = ti.grid;
+    st->walk_kind = (int)kWalkDense;
+    st->leaves = (int)std::min<uint64_t>(count, 0x7fffffffu);
+    st->est_ops_per_step = ti.ops;
+  }
+  return SUP_OK;
+}
+
+int sup_threshold_sample(const double* B, int M, const double* zeta, const double* het, uint64_t nsamples, uint64_t sample0,
+                         uint64_t seed, const sup_opts* o_in, int on_cpu, int32_t* out, double* weights, sup_stats* st) {
+  auto t0 = std::chrono::steady_clock::now();
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  ThrInfo gi;
+  if (int rc = threshold_sample(B, M, zeta, het, nsamples, sample0, seed, o, on_cpu != 0, out, weights, &gi)) return rc;
+  if (st) {
+    std::memset(st, 0, sizeof(*st));
+    st->kernel_ms = gi.kernel_ms;
+    st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    st->gray_steps = gi.visited;
+    st->visited_steps = gi.visited;
+    st->devices_used = gi.devices;
+    st->walk_kind = (int)kWalkDense;
+    st->leaves = (int)std::min<uint64_t>(nsamples, 0x7fffffffu);
+    st->est_ops_per_step = gi.ops;
+    st->partials[0] = gi.each_ms;         // wall time inside the ragged loop torontonian calls
+    st->partials[1] = gi.host_ms;         // wall time of the host stage: lists, gamma rows, weights and draws
+    st->partials[2] = (double)gi.failed;  // samples that ended in -1
+  }
+  return SUP_OK;
+}
+
 double sup_ltor_exp(double x) { return ltor_exp(x); }
 
 int sup_ltor_exp_device(const double* x, uint64_t count, double* out, int device_id) {

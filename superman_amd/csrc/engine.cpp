@@ -1823,6 +1823,82 @@ int run_loop_torontonian(int dev, const LtorIn& in, int n, uint64_t first, uint6
   return timed_sync(c, kernel_ms);
 }
 
+// The ragged loop torontonian kernel (walk_ltore in walk_ltor.hip) on one slab
+// of items of any orders: O, the slab's gamma rows (behind O), the lists and
+// the descriptors go up once, then the ragged prepare, the walk over the
+// slab's one queue and the per-item fold, and one download brings 8 bytes per
+// item into out.  The buffers are run_loop_torontonian's, the descriptors in
+// the collision-aware walk's.
+int run_loop_torontonian_each(int dev, const LtorEachIn& in, const LtorEachSlab& S, double* out, double* kernel_ms,
+                              int* grid_out) {
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (grid_out) *grid_out = 0;
+  const uint64_t K = S.items.size();
+  if (K == 0) return SUP_OK;
+  if (!out || !in.O || !in.gamma || in.M < 1 || S.stride < 1 || S.modes.size() != K * (uint64_t)S.stride || S.max_n < 1 ||
+      S.max_n > SUP_LOOP_TORONTONIAN_MAX_DEVICE_N || ltor_lds_bytes(S.max_n) > 65536 || S.rows < 1 ||
+      S.row_lo + S.rows > in.ngamma || S.chunks < K || S.chunks > 0x7fffffffull) {
+    set_error("run_loop_torontonian_each: bad request");
+    return SUP_EINVAL;
+  }
+  // the kernel trusts the descriptors: every one is checked here
+  uint64_t goff = 0, coff = 0;
+  for (const LtorItem& d : S.items) {
+    if (d.n < 1 || d.n > (unsigned)S.max_n || d.nn != (unsigned)tor_nn((int)d.n) || d.llog != (unsigned)tor_chunk_log((int)d.n) ||
+        d.cm != ltor_item_chunks((int)d.n) || d.g_off != goff || d.chunk0 != coff || d.row >= S.rows) {
+      set_error("run_loop_torontonian_each: bad item descriptor");
+      return SUP_EINVAL;
+    }
+    goff += ltor_g_doubles((int)d.n), coff += d.cm;
+  }
+  if (goff != S.g_doubles || coff != S.chunks) {
+    set_error("run_loop_torontonian_each: bad slab totals");
+    return SUP_EINVAL;
+  }
+  const size_t o_doubles = (size_t)8 * in.M * in.M, gm_doubles = (size_t)4 * in.M * (size_t)S.rows;
+  CtxGuard guard;
+  int rc = guard.open(dev, "device buffers");
+  if (rc) return rc;
+  DeviceCtx* c = guard.c;
+  int occ = 0;
+  SUP_HIP(ltore_occupancy(S.max_n, &occ));
+  if ((rc = ensure(c->d_cbtab, c->cbtab_cap, (size_t)S.g_doubles))) return rc;
+  if ((rc = ensure(c->d_cbidx, c->cbidx_cap, S.modes.size()))) return rc;
+  if ((rc = ensure(c->d_cbU, c->cbU_cap, o_doubles + gm_doubles))) return rc;
+  if ((rc = ensure(c->d_chunk, c->chunk_cap, (size_t)(2 * S.chunks)))) return rc;
+  if ((rc = ensure(c->d_cbout, c->cbout_cap, (size_t)K))) return rc;
+  if ((rc = ensure(c->d_fock, c->fock_cap, (size_t)K * (sizeof(LtorItem) / 16)))) return rc;
+  hipStream_t s = c->stream;
+  c->tables_uid = 0;  // the walk leaves head 0 nonzero
+  c->head_zero[0] = false;
+  SUP_HIP(hipMemcpyAsync(c->d_cbU, in.O, o_doubles * sizeof(double), hipMemcpyHostToDevice, s));
+  SUP_HIP(hipMemcpyAsync(c->d_cbU + o_doubles, in.gamma + 4ull * (uint64_t)in.M * S.row_lo, gm_doubles * sizeof(double),
+                         hipMemcpyHostToDevice, s));
+  SUP_HIP(hipMemcpyAsync(c->d_cbidx, S.modes.data(), S.modes.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  SUP_HIP(hipMemcpyAsync(c->d_fock, S.items.data(), (size_t)K * sizeof(LtorItem), hipMemcpyHostToDevice, s));
+  SUP_HIP(hipMemsetAsync(c->d_counter, 0, sizeof(unsigned), s));
+  const uint64_t resident = (uint64_t)c->cus * (uint64_t)std::max(occ, 1);
+  const char* fg = std::getenv("SUP_WALK_GROUP");  // tests, read per call: slots per ticket (the bits do not change)
+  const LaunchGeom geo = walk_geometry(S.chunks, resident, 1, false, fg ? std::max(1, std::atoi(fg)) : 0);
+  LtorEachParams p{};
+  p.G = c->d_cbtab;
+  p.items = reinterpret_cast<const LtorItem*>(c->d_fock);
+  p.item_count = (unsigned)K;
+  p.group = geo.group;
+  p.chunk_count = S.chunks;
+  p.chunk_out = c->d_chunk;
+  p.counter = c->d_counter;
+  SUP_HIP(hipEventRecord(c->ev0, s));
+  SUP_ON_DEVICE(c->dev, "ragged loop torontonian launch");
+  SUP_HIP(launch_ltore_prepare(c->d_cbU, in.M, c->d_cbU + o_doubles, c->d_cbidx, S.stride, p.items, K, c->d_cbtab, s));
+  SUP_HIP(launch_ltore(p, S.max_n, (int)geo.grid, s));
+  SUP_HIP(launch_ltore_fold(c->d_chunk, p.items, K, c->d_cbout, s));
+  SUP_HIP(hipEventRecord(c->ev1, s));
+  SUP_HIP(hipMemcpyAsync(out, c->d_cbout, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (grid_out) *grid_out = (int)geo.grid;
+  return timed_sync(c, kernel_ms);
+}
+
 // A table of 2^n doubles lives in d_cbout; one above kTableKeepBytes is given
 // back after the call instead of staying with the context.
 constexpr size_t kTableKeepBytes = (size_t)256 << 20;

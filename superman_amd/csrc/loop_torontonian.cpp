@@ -10,6 +10,8 @@
 // factor and the border row of the current subset and, stepping z upwards,
 // recomputes only the rows and border columns at and below the highest
 // position that changed.  Result k is a function of (O, gamma, modes[k]) only.
+// sup_loop_torontonian_each, at the end of the file, runs lists
+// of different orders, each with its own gamma row, through the same chunks.
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
@@ -321,6 +323,232 @@ int loop_torontonian(const LtorIn& in, int n, uint64_t count, bool range, uint64
   ti.kernel_ms = *std::max_element(dms.begin(), dms.end());
   ti.grid = dgrid[0];
   ti.devices = G;
+  if (info) *info = ti;
+  return SUP_OK;
+}
+
+// ---- the ragged batch: sup_loop_torontonian_each ----
+
+static_assert(kTorMaxN <= SUP_LOOP_TORONTONIAN_MAX_DEVICE_N, "every order the ragged entry takes runs on the device");
+
+size_t ltor_item_bytes(int n, int stride) {
+  return (size_t)(8 * ltor_g_doubles(n)) + (size_t)ltor_item_chunks(n) * 16 + (size_t)stride * 4 + 8 + sizeof(LtorItem);
+}
+size_t ltor_slab_cap_bytes() { return kLtorSlabCapBytes; }
+
+namespace {
+
+template <class F>
+void ltor_threads(int T, F&& work) {
+  std::vector<std::thread> th;
+  for (int w = 1; w < T; ++w) th.emplace_back(work);
+  work();
+  for (auto& t : th) t.join();
+}
+
+// The host twin of one slab: every item gathered as loop_torontonian's twin
+// gathers it, the queue's slots over the threads (slot chunk0 + c of an item
+// is ltor_chunk c of that item alone), then fock_fold over each item's slots.
+void ltor_each_cpu(const LtorEachIn& in, const LtorEachSlab& S, int tail_env, int threads, double* out) {
+  const uint64_t K = S.items.size();
+  std::vector<std::vector<double>> Gs((size_t)K);
+  std::vector<double> parts((size_t)(2 * S.chunks), 0.0);
+  {
+    std::atomic<uint64_t> next{0};
+    ltor_threads((int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)threads, K)), [&]() {
+      for (uint64_t k = next.fetch_add(1); k < K; k = next.fetch_add(1)) {
+        LtorIn li;
+        li.O = in.O, li.M = in.M;
+        li.gamma = in.gamma + 4ull * (uint64_t)in.M * (S.row_lo + S.items[(size_t)k].row);
+        ltor_gather(li, S.modes.data() + k * (uint64_t)S.stride, (int)S.items[(size_t)k].n, Gs[(size_t)k]);
+      }
+    });
+  }
+  std::atomic<uint64_t> next{0};
+  ltor_threads((int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)threads, S.chunks)), [&]() {
+    int have_nn = 0;
+    std::vector<LtorState> st;  // one state, rebuilt when the padded order changes
+    for (uint64_t a = next.fetch_add(1); a < S.chunks; a = next.fetch_add(1)) {
+      const auto it = std::upper_bound(S.items.begin(), S.items.end(), a,
+                                       [](uint64_t v, const LtorItem& d) { return v < (uint64_t)d.chunk0; });
+      const LtorItem& d = *(it - 1);
+      const int n = (int)d.n, nn = (int)d.nn;
+      if (nn != have_nn) {
+        st.clear();
+        st.emplace_back(nn);
+        have_nn = nn;
+      }
+      const int tail = tail_env < 0 ? -1 : std::min(tail_env, nn);
+      parts[(size_t)(2 * a)] = ltor_chunk(Gs[(size_t)(&d - S.items.data())].data(), n, nn, tail, a - d.chunk0, 0, 1ull << n, st[0]);
+    }
+  });
+  for (uint64_t k = 0; k < K; ++k)
+    out[k] = fock_fold(parts.data() + 2 * (uint64_t)S.items[(size_t)k].chunk0, S.items[(size_t)k].cm).re;
+}
+
+}  // namespace
+
+int loop_torontonian_each(const LtorEachIn& in, uint64_t count, const sup_opts& o, bool on_cpu, double* out, TorInfo* info) {
+  const std::string who = "sup_loop_torontonian_each";
+  if (!out || !in.O || !in.gamma || !in.modes || !in.n) {
+    set_error(who + ": null pointer");
+    return SUP_EINVAL;
+  }
+  if (in.M < 1) {
+    set_error(who + ": O must have at least two rows (M = " + std::to_string(in.M) + ")");
+    return SUP_EINVAL;
+  }
+  for (uint64_t k = 0; k < count; ++k) {
+    const int32_t nk = in.n[k];
+    if (nk < 0 || nk > kTorMaxN) {
+      set_error(who + ": n[k = " + std::to_string(k) + "] = " + std::to_string(nk) + " outside [0, 32]");
+      return SUP_EINVAL;
+    }
+    if (nk > in.stride) {
+      set_error(who + ": stride = " + std::to_string(in.stride) + " < n[k = " + std::to_string(k) + "] = " + std::to_string(nk));
+      return SUP_EINVAL;
+    }
+    const int64_t row = in.gamma_of ? (int64_t)in.gamma_of[k] : (int64_t)k;
+    if (row < 0 || (uint64_t)row >= in.ngamma) {
+      set_error(who + ": gamma_of[k = " + std::to_string(k) + "] = " + std::to_string(row) + " outside [0, " +
+                std::to_string(in.ngamma) + ")");
+      return SUP_EINVAL;
+    }
+    const int32_t* s = in.modes + k * (uint64_t)in.stride;
+    for (int j = 0; j < nk; ++j) {
+      if (s[j] < 0 || s[j] >= in.M) {
+        set_error(who + ": modes[k = " + std::to_string(k) + "][position " + std::to_string(j) + "] = " +
+                  std::to_string(s[j]) + " outside [0, " + std::to_string(in.M) + ")");
+        return SUP_EINVAL;
+      }
+      for (int i = 0; i < j; ++i)
+        if (s[i] == s[j]) {
+          set_error(who + ": modes[k = " + std::to_string(k) + "] names mode " + std::to_string(s[j]) + " at positions " +
+                    std::to_string(i) + " and " + std::to_string(j) + ": the modes of a list must be distinct");
+          return SUP_EINVAL;
+        }
+    }
+  }
+  // SUP_LTOR_EACH_SLAB (tests, read per call): items per slab at most
+  uint64_t slab_max = ~0ull;
+  if (const char* e = std::getenv("SUP_LTOR_EACH_SLAB")) {
+    char* end = nullptr;
+    const long long v = std::strtoll(e, &end, 10);
+    if (end == e || *end != '\0' || v < 1) {
+      set_error(who + ": SUP_LTOR_EACH_SLAB = \"" + std::string(e) + "\" is not a positive count of items");
+      return SUP_EINVAL;
+    }
+    slab_max = (uint64_t)v;
+  }
+  TorInfo ti;
+  if (info) *info = ti;
+  int G = 1;
+  if (!on_cpu) {
+    int ndev = 0;
+    int rc = device_count(&ndev);
+    if (rc) return rc;
+    if (ndev == 0) {
+      set_error("no HIP device available (" + who + " has no CPU fallback; on_cpu = 1 runs host threads)");
+      return SUP_ENODEV;
+    }
+    if (o.device_id < 0 || o.device_id >= ndev) {
+      set_error(who + ": device_id out of range");
+      return SUP_EINVAL;
+    }
+    G = std::max(1, std::min(o.gpu_num, ndev - o.device_id));
+  }
+  try {
+    // the items that walk: an item of order 0 is the empty list's f(0) = 1
+    std::vector<uint64_t> live;
+    double ops_of[kTorMaxN + 1], ops_sum = 0.0;
+    for (int n = 0; n <= kTorMaxN; ++n) ops_of[n] = -1.0;
+    for (uint64_t k = 0; k < count; ++k) {
+      const int n = in.n[k];
+      if (n == 0) {
+        out[k] = 1.0;
+        continue;
+      }
+      live.push_back(k);
+      if (ops_of[n] < 0.0) ops_of[n] = ltor_ops(n);
+      ti.subsets += 1ull << n;
+      ops_sum += (double)(1ull << n) * ops_of[n];
+    }
+    const uint64_t L = live.size();
+    if (L == 0) return SUP_OK;
+    ti.ops = ops_sum / (double)ti.subsets;
+    G = (int)std::min<uint64_t>((uint64_t)G, L);
+    const char* tw = std::getenv("LTOR_TWIN_TAIL");  // as loop_torontonian's twin
+    const int tail = tw ? std::max(std::atoi(tw), 0) : -1;
+    std::vector<int> drc(G, SUP_OK), dgrid(G, 0);
+    std::vector<double> dms(G, 0.0);
+    std::vector<std::string> derr(G);
+    // live items [a, b) of a device in slabs under the caps; orders mix freely
+    auto work = [&](int g) {
+      const uint64_t a = L * (uint64_t)g / (uint64_t)G, b = L * (uint64_t)(g + 1) / (uint64_t)G;
+      try {
+        std::vector<double> res;
+        for (uint64_t i = a; i < b && !drc[g];) {
+          LtorEachSlab S;
+          S.stride = in.stride;
+          size_t bytes = 0;
+          const uint64_t i0 = i;
+          uint64_t lo = ~0ull, hi = 0;
+          for (; i < b && i - i0 < slab_max; ++i) {
+            const uint64_t k = live[i];
+            const int n = in.n[k];
+            const size_t add = ltor_item_bytes(n, in.stride);
+            const uint64_t cm = ltor_item_chunks(n);
+            if (i > i0 && (bytes + add > kLtorSlabCapBytes || S.chunks + cm > 0x7fffffffull)) break;
+            LtorItem d{};
+            d.g_off = S.g_doubles, d.chunk0 = (unsigned)S.chunks, d.cm = (unsigned)cm;
+            d.n = (unsigned)n, d.nn = (unsigned)tor_nn(n), d.llog = (unsigned)tor_chunk_log(n);
+            const uint64_t row = in.gamma_of ? (uint64_t)in.gamma_of[k] : k;
+            lo = std::min(lo, row), hi = std::max(hi, row);
+            S.items.push_back(d);
+            S.modes.resize(S.modes.size() + (size_t)in.stride, 0);  // the entries past n[k] are not read
+            std::copy(in.modes + k * (uint64_t)in.stride, in.modes + k * (uint64_t)in.stride + n, S.modes.end() - in.stride);
+            S.g_doubles += ltor_g_doubles(n), S.chunks += cm, S.max_n = std::max(S.max_n, n);
+            bytes += add;
+          }
+          // the device takes rows [lo, hi] of gamma alone
+          S.row_lo = lo, S.rows = hi - lo + 1;
+          for (uint64_t q = i0; q < i; ++q)
+            S.items[(size_t)(q - i0)].row = (unsigned)((in.gamma_of ? (uint64_t)in.gamma_of[live[q]] : live[q]) - lo);
+          res.assign((size_t)(i - i0), 0.0);
+          if (on_cpu) {
+            ltor_each_cpu(in, S, tail, std::max(o.threads, 1), res.data());
+          } else {
+            double ms = 0.0;
+            drc[g] = run_loop_torontonian_each(o.device_id + g, in, S, res.data(), &ms, &dgrid[g]);
+            if (drc[g]) derr[g] = last_error();
+            dms[g] += ms;
+          }
+          if (!drc[g])
+            for (uint64_t q = i0; q < i; ++q) out[live[q]] = res[(size_t)(q - i0)];
+        }
+      } catch (const std::bad_alloc&) {
+        derr[g] = "out of host memory for a slab's matrices and partials";
+        drc[g] = SUP_ENOMEM;
+      }
+    };
+    std::vector<std::thread> th;
+    for (int g = 1; g < G; ++g) th.emplace_back(work, g);
+    work(0);
+    for (auto& t : th) t.join();
+    for (int g = 0; g < G; ++g)
+      if (drc[g]) {
+        set_error(derr[g]);
+        return drc[g];
+      }
+    if (!on_cpu) {
+      ti.kernel_ms = *std::max_element(dms.begin(), dms.end());
+      ti.grid = dgrid[0];
+      ti.devices = G;
+    }
+  } catch (const std::bad_alloc&) {
+    set_error(who + ": out of host memory for the items' lists");
+    return SUP_ENOMEM;
+  }
   if (info) *info = ti;
   return SUP_OK;
 }

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/superman.h"
 #include "ltor.hpp"
 #include "torontonian.hpp"
@@ -41,6 +43,55 @@ int run_ltor_exp(int dev, const double* x, uint64_t count, double* out);
 int loop_torontonian(const LtorIn& in, int n, uint64_t count, bool range, uint64_t z_begin, uint64_t z_end,
                      const sup_opts& o, bool on_cpu, double* out, TorInfo* info);
 int loop_torontonian_plan(int n, uint64_t* subsets, double* est_ops);
+
+// ---- the ragged batch: sup_loop_torontonian_each ----
+// Item k is the loop torontonian of the list modes[k stride .. + n[k]) with row
+// gamma_of[k] (null: row k) of gamma (ngamma rows of 2M complex).
+struct LtorEachIn {
+  const double* O = nullptr;
+  int M = 0;
+  const double* gamma = nullptr;
+  uint64_t ngamma = 0;
+  const int32_t* gamma_of = nullptr;
+  const int32_t* modes = nullptr;
+  int stride = 0;
+  const int32_t* n = nullptr;
+};
+// A slab of walking items: their descriptors, their lists (stride entries
+// each) and the rows [row_lo, row_lo + rows) of gamma their descriptors count from.
+struct LtorEachSlab {
+  std::vector<LtorItem> items;
+  std::vector<int32_t> modes;
+  int stride = 0, max_n = 0;
+  uint64_t row_lo = 0, rows = 0, g_doubles = 0, chunks = 0;
+};
+// out[k] = item k: the bits of loop_torontonian on that item alone, exactly 1.0
+// at n[k] = 0.  Everything is checked before any work.
+int loop_torontonian_each(const LtorEachIn& in, uint64_t count, const sup_opts& o, bool on_cpu, double* out, TorInfo* info);
+// The bytes an item of order n >= 1 adds to a slab and the cap a slab is filled to.
+size_t ltor_item_bytes(int n, int stride);
+size_t ltor_slab_cap_bytes();
+// One slab on device `dev`: out[i] = item i of the slab.
+int run_loop_torontonian_each(int dev, const LtorEachIn& in, const LtorEachSlab& S, double* out, double* kernel_ms, int* grid);
+
+struct ThrInfo {
+  double kernel_ms = 0.0, each_ms = 0.0, host_ms = 0.0;
+  int devices = 0;
+  uint64_t visited = 0, failed = 0;
+  double ops = 0.0;  // the subset-weighted mean of ltor_ops over every call's items
+};
+// nsamples click patterns of the pure Gaussian state (B, zeta[s]) on threshold
+// detectors by the chain rule with the heterodyne outcomes het
+// (sup_threshold_sample; threshold_sample.cpp).
+int threshold_sample(const double* B, int M, const double* zeta, const double* het, uint64_t nsamples, uint64_t sample0,
+                     uint64_t seed, const sup_opts& o, bool on_cpu, int32_t* out, double* weights, ThrInfo* info);
+
+// walk_ltor.hip.  The ragged batch's launchers.
+hipError_t launch_ltore(const LtorEachParams& p, int max_n, int grid, hipStream_t s);
+hipError_t ltore_occupancy(int max_n, int* blocks_per_cu);
+hipError_t launch_ltore_prepare(const double* O, int M, const double* gammas, const int32_t* modes, int stride,
+                                const LtorItem* items, uint64_t K, double* G, hipStream_t s);
+hipError_t launch_ltore_fold(const double* parts, const LtorItem* items, uint64_t K, double* out, hipStream_t s);
 
 // walk_ltor.hip.  p.G: ltor_g_doubles(n) doubles per list.
 hipError_t launch_ltor(const TorParams& p, int grid, hipStream_t s);

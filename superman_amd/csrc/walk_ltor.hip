@@ -23,6 +23,9 @@
 //               factor, closes d, and multiplies ltor_exp(-0.5 d) in last.
 // G, the list's gathered matrix with the border as its last row, stays in
 // global memory.  Resource report: profiles/loop_torontonian/walk_ltor_resources.log.
+// walk_ltore (sup_loop_torontonian_each) walks the same chunks
+// for lists of different orders in one queue, with ltore_prepare and
+// ltore_fold beside it: profiles/threshold_chain/walk_ltore_resources.log.
 #include "cx.hpp"
 #include "loop_torontonian.hpp"
 #include "ltor.hpp"
@@ -166,22 +169,59 @@ __device__ __forceinline__ double ltor_tail(const double* S, double f, uint32_t 
   return f * ltor_exp(-0.5 * d);
 }
 
-// TABLE (tortab.hpp): the lane that holds z stores its unsigned f(z) to
-// chunk_out[z], the 2^n table of the one list, and the sign, the butterfly, the
-// chunk partial and the fold are left out.
-template <bool TABLE>
-__device__ __forceinline__ void walk_ltor_body(const TorParams& p) {
-  extern __shared__ double ltor_lds[];
-  const uint32_t lane = threadIdx.x;
-  const uint32_t n = p.n, nn = p.nn, H = nn - (uint32_t)kLtorW, PM = 2u * H, N = 2u * nn;
+// The wave's LDS carved for PM prefix rows (loop_torontonian.hpp ltor_lds_bytes).
+__device__ __forceinline__ LtorLds ltor_carve(double* lds, uint32_t PM) {
   LtorLds m;
-  m.Lp = ltor_lds;
+  m.Lp = lds;
   m.T = m.Lp + (size_t)PM * (PM > 0u ? PM - 1u : 0u);
   m.S = m.T + 2 * (size_t)(kLtorR + 1) * PM;
   m.rho = m.S + 2 * (size_t)kLtorSub * kLtorE;
   m.prod = m.rho + PM;
   m.ps = m.prod + PM + 1u;
   m.prow = (int*)(m.ps + kLtorSub);
+  return m;
+}
+
+// The partial of the z in [zlo, zhi) of one wave-chunk of a list of order n
+// (zhi <= 2^n): its 64-aligned groups ascending from +0.
+// TABLE (tortab.hpp): the lane that holds z stores its unsigned f(z) to
+// table[z], the 2^n table of the one list, and the sign, the butterfly and the
+// partial are left out.
+template <bool TABLE>
+__device__ __forceinline__ double ltor_walk_chunk(const LtorLds& m, const double* G, uint32_t n, uint32_t N, uint32_t PM,
+                                                  uint32_t H, uint64_t zlo, uint64_t zhi, double* table) {
+  const uint32_t lane = threadIdx.x;
+  double acc = 0.0;
+  bool have = false;
+  uint32_t hp = 0;
+  for (uint64_t grp = zlo >> 6; (grp << 6) < zhi; ++grp) {
+    for (uint32_t q = 0; q < (uint32_t)kLtorSub; ++q) {
+      const uint32_t h = (uint32_t)(((grp << 6) >> kLtorW) + q);
+      if (((uint64_t)h << kLtorW) >= zhi) break;  // z < 2^n below: h stays below 2^H
+      ltor_advance(m, G, N, PM, H, h, hp, have, q);
+      hp = h, have = true;
+    }
+    const uint64_t z = (grp << 6) + lane;
+    double f = 0.0;
+    if (z >= zlo && z < zhi) {
+      const uint32_t q = lane >> kLtorW;
+      f = ltor_tail(m.S + 2 * (size_t)q * kLtorE, m.ps[q], lane & ((1u << kLtorW) - 1u));
+      if (TABLE) table[z] = f;
+      else if ((n - (uint32_t)__builtin_popcountll(z)) & 1u) f = -f;
+    }
+    if (!TABLE) acc = acc + ltor_wave_sum(f);
+    __syncthreads();  // the next group's advance overwrites S
+  }
+  return acc;
+}
+
+// TABLE: the fold is left out too; p.chunk_out is the table.
+template <bool TABLE>
+__device__ __forceinline__ void walk_ltor_body(const TorParams& p) {
+  extern __shared__ double ltor_lds[];
+  const uint32_t lane = threadIdx.x;
+  const uint32_t n = p.n, nn = p.nn, H = nn - (uint32_t)kLtorW, PM = 2u * H, N = 2u * nn;
+  const LtorLds m = ltor_carve(ltor_lds, PM);
   if (lane == 0) m.prod[0] = 1.0;
   __syncthreads();
   for (uint32_t g = next_chunk(p.counter); (uint64_t)g * p.group < p.chunk_count; g = next_chunk(p.counter)) {
@@ -195,27 +235,7 @@ __device__ __forceinline__ void walk_ltor_body(const TorParams& p) {
       uint64_t zlo = c << p.llog, zhi = (c + 1ull) << p.llog;
       if (zlo < p.z_begin) zlo = p.z_begin;
       if (zhi > p.z_end) zhi = p.z_end;
-      double acc = 0.0;
-      bool have = false;
-      uint32_t hp = 0;
-      for (uint64_t grp = zlo >> 6; (grp << 6) < zhi; ++grp) {
-        for (uint32_t q = 0; q < (uint32_t)kLtorSub; ++q) {
-          const uint32_t h = (uint32_t)(((grp << 6) >> kLtorW) + q);
-          if (((uint64_t)h << kLtorW) >= zhi) break;  // z < 2^n below: h stays below 2^H
-          ltor_advance(m, G, N, PM, H, h, hp, have, q);
-          hp = h, have = true;
-        }
-        const uint64_t z = (grp << 6) + lane;
-        double f = 0.0;
-        if (z >= zlo && z < zhi) {
-          const uint32_t q = lane >> kLtorW;
-          f = ltor_tail(m.S + 2 * (size_t)q * kLtorE, m.ps[q], lane & ((1u << kLtorW) - 1u));
-          if (TABLE) p.chunk_out[z] = f;
-          else if ((n - (uint32_t)__builtin_popcountll(z)) & 1u) f = -f;
-        }
-        if (!TABLE) acc = acc + ltor_wave_sum(f);
-        __syncthreads();  // the next group's advance overwrites S
-      }
+      const double acc = ltor_walk_chunk<TABLE>(m, G, n, N, PM, H, zlo, zhi, p.chunk_out);
       if (lane == j) keepv = acc;
     }
     const uint64_t a = (uint64_t)g * p.group + lane;
@@ -228,6 +248,53 @@ __device__ __forceinline__ void walk_ltor_body(const TorParams& p) {
 
 __global__ __launch_bounds__(kLtorBlock) void walk_ltor(TorParams p) { walk_ltor_body<false>(p); }
 __global__ __launch_bounds__(kLtorBlock) void walk_ltor_table(TorParams p) { walk_ltor_body<true>(p); }
+
+// A descriptor field is the same in every lane: say so, and it lives in a scalar register.
+__device__ __forceinline__ uint32_t ltor_uniform(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// walk_ltore: the ragged batch (sup_loop_torontonian_each).  The
+// queue holds the wave-chunks of every item of the slab one after the other
+// (item i: slots [chunk0, chunk0 + cm)); a ticket finds the item of its first
+// slot by bisection over chunk0 and steps on from there.  The order, the
+// padded order, the chunk size and the place of the item's G come from its
+// descriptor, all wave-uniform; the LDS is carved again for every chunk from
+// the item's own PM, and the chunk is walk_ltor's.
+__global__ __launch_bounds__(kLtorBlock) void walk_ltore(LtorEachParams p) {
+  extern __shared__ double ltor_lds[];
+  const uint32_t lane = threadIdx.x;
+  for (uint32_t g = next_chunk(p.counter); (uint64_t)g * p.group < p.chunk_count; g = next_chunk(p.counter)) {
+    const uint32_t a0 = g * p.group;  // the queue has fewer than 2^31 slots
+    uint32_t it = 0, end = p.item_count;  // the last item with chunk0 <= a0
+    while (end - it > 1u) {
+      const uint32_t mid = (it + end) >> 1;
+      if (p.items[mid].chunk0 <= a0) it = mid;
+      else end = mid;
+    }
+    double keepv = 0.0;  // lane j keeps the partial of slot a0 + j
+    for (uint32_t j = 0; j < p.group; ++j) {
+      const uint32_t a = a0 + j;
+      if (a >= (uint32_t)p.chunk_count) break;
+      while (it + 1u < p.item_count && a >= p.items[it + 1u].chunk0) ++it;
+      const LtorItem* d = p.items + it;
+      const uint32_t n = ltor_uniform(d->n), nn = ltor_uniform(d->nn), llog = ltor_uniform(d->llog);
+      const uint32_t c = ltor_uniform(a - d->chunk0);
+      const double* G = p.G + (((uint64_t)ltor_uniform((uint32_t)(d->g_off >> 32)) << 32) | ltor_uniform((uint32_t)d->g_off));
+      const uint32_t H = nn - (uint32_t)kLtorW, PM = 2u * H, N = 2u * nn;
+      const LtorLds m = ltor_carve(ltor_lds, PM);
+      if (lane == 0) m.prod[0] = 1.0;
+      __syncthreads();
+      uint64_t zlo = (uint64_t)c << llog, zhi = ((uint64_t)c + 1ull) << llog;
+      if (zhi > (1ull << n)) zhi = 1ull << n;
+      const double acc = ltor_walk_chunk<false>(m, G, n, N, PM, H, zlo, zhi, nullptr);
+      if (lane == j) keepv = acc;
+    }
+    const uint32_t a = a0 + lane;
+    if (lane < p.group && a < (uint32_t)p.chunk_count) {
+      p.chunk_out[2 * (uint64_t)a] = keepv;
+      p.chunk_out[2 * (uint64_t)a + 1] = 0.0;
+    }
+  }
+}
 
 // ltor_prepare: one block per list writes its gathered matrix (tor.hpp
 // tor_entry) and border row (ltor.hpp ltor_border), the host twin's own
@@ -243,6 +310,33 @@ __global__ __launch_bounds__(256) void ltor_prepare(const double* __restrict__ O
     g[2 * (uint64_t)e] = v.re;
     g[2 * (uint64_t)e + 1] = v.im;
   }
+}
+
+// ltore_prepare: ltor_prepare with the item's own list (its first n entries),
+// order, gamma row and place in G.
+__global__ __launch_bounds__(256) void ltore_prepare(const double* __restrict__ O, int Mo, const double* __restrict__ gammas,
+                                                     const int32_t* __restrict__ modes, int stride,
+                                                     const LtorItem* __restrict__ items, double* __restrict__ G) {
+  const LtorItem d = items[blockIdx.x];
+  const int n = (int)d.n;
+  const uint32_t N = 2u * d.nn;
+  double* g = G + d.g_off;
+  const int32_t* s = modes + (uint64_t)blockIdx.x * (uint64_t)stride;
+  const double* gamma = gammas + 4ull * (uint64_t)Mo * (uint64_t)d.row;
+  for (uint32_t e = threadIdx.x; e < N * (N + 1u); e += 256u) {
+    const uint32_t R = e / N, C = e % N;
+    const cx v = R < N ? tor_entry(O, Mo, s, n, (int)R, (int)C) : ltor_border(gamma, Mo, s, n, (int)C);
+    g[2 * (uint64_t)e] = v.re;
+    g[2 * (uint64_t)e + 1] = v.im;
+  }
+}
+
+// ltore_fold: tor_fold over each item's own slots.
+__global__ __launch_bounds__(256) void ltore_fold(const double* __restrict__ parts, const LtorItem* __restrict__ items,
+                                                  uint64_t K, double* __restrict__ out) {
+  const uint64_t k = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (k >= K) return;
+  out[k] = fock_fold(parts + 2 * (uint64_t)items[k].chunk0, items[k].cm).re;
 }
 
 // ltor_exp_each: out[i] = ltor_exp(x[i]) (sup_ltor_exp_device, the tests' helper).
@@ -287,6 +381,35 @@ hipError_t launch_ltor_prepare(const double* O, int M, const double* gamma, cons
                                double* G, hipStream_t s) {
   if (M < 1 || n < 1 || n > kTorMaxN || K == 0 || K > 0x7fffffffull || !O || !gamma || !modes || !G) return hipErrorInvalidValue;
   hipLaunchKernelGGL(ltor_prepare, dim3((unsigned)K), dim3(256), 0, s, O, M, gamma, modes, n, G);
+  return hipGetLastError();
+}
+
+// The host has checked every descriptor (loop_torontonian.cpp ltor_each_slab);
+// max_n: the slab's largest order, whose LDS the launch asks for.
+hipError_t launch_ltore(const LtorEachParams& p, int max_n, int grid, hipStream_t s) {
+  if (grid < 1 || max_n < 1 || max_n > SUP_LOOP_TORONTONIAN_MAX_DEVICE_N || ltor_lds_bytes(max_n) > 65536 || !p.G || !p.items ||
+      p.item_count < 1 || p.chunk_count < p.item_count || p.chunk_count > 0x7fffffffull || p.group < 1 || p.group > 64 ||
+      !p.chunk_out || !p.counter)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(walk_ltore, dim3(grid), dim3(kLtorBlock), ltor_lds_bytes(max_n), s, p);
+  return hipGetLastError();
+}
+
+hipError_t ltore_occupancy(int max_n, int* blocks_per_cu) {
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, walk_ltore, kLtorBlock, ltor_lds_bytes(max_n));
+}
+
+hipError_t launch_ltore_prepare(const double* O, int M, const double* gammas, const int32_t* modes, int stride,
+                                const LtorItem* items, uint64_t K, double* G, hipStream_t s) {
+  if (M < 1 || stride < 1 || K == 0 || K > 0x7fffffffull || !O || !gammas || !modes || !items || !G) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ltore_prepare, dim3((unsigned)K), dim3(256), 0, s, O, M, gammas, modes, stride, items, G);
+  return hipGetLastError();
+}
+
+hipError_t launch_ltore_fold(const double* parts, const LtorItem* items, uint64_t K, double* out, hipStream_t s) {
+  const uint64_t blocks = (K + 255) / 256;
+  if (K == 0 || blocks > 0x7fffffffull || !parts || !items || !out) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ltore_fold, dim3((unsigned)blocks), dim3(256), 0, s, parts, items, K, out);
   return hipGetLastError();
 }
 

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SUP_ABI_VERSION 28  /* 28: sup_loop_torontonian_each, sup_threshold_sample; 27: sup_loop_hafnian_table, sup_loop_hafnian_table_plan, SUP_LHAF_TABLE_MAX_ENTRIES; 26: sup_loop_hafnian_complex_each, sup_gbs_sample; 25: sup_torontonian_table, sup_loop_torontonian_table, sup_mobius_subsets, SUP_TORONTONIAN_TABLE_MAX_N; 24: sup_loop_torontonian, sup_loop_torontonian_range, sup_loop_torontonian_plan, sup_ltor_exp, sup_ltor_exp_device, SUP_LOOP_TORONTONIAN_MAX_DEVICE_N; 23: sup_hafnian_complex_exact; 22: sup_torontonian, sup_torontonian_range, sup_torontonian_plan, SUP_TORONTONIAN_MAX_DEVICE_N; 21: sup_hafnian_complex_pt, sup_loop_hafnian_complex_pt, sup_hafnian_complex_pt_range, sup_hafnian_complex_pt_plan, SUP_HAFNIAN_PT_MAX_DEVICE_N; 20: sup_hafnian_complex, sup_loop_hafnian_complex, sup_hafnian_complex_plan; 19: sup_perman_complex_exact, sup_perman_complex_exact_range, SUP_CPLX_EXACT_MAX_DEVICE_N; 18: sup_perman_complex_quad, sup_perman_complex_quad_range, SUP_CPLX_QUAD_MAX_DEVICE_N; 17:sup_perman_complex_fock_minors, sup_perman_complex_fock_minors_plan, sup_boson_sample_fock; 16: sup_plan_census; 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
+#define SUP_ABI_VERSION 29  /* 29: sup_hafnian_complex_quad, sup_loop_hafnian_complex_quad, SUP_HAFNIAN_QUAD_MAX_DEVICE_N; 28: sup_loop_torontonian_each, sup_threshold_sample; 27: sup_loop_hafnian_table, sup_loop_hafnian_table_plan, SUP_LHAF_TABLE_MAX_ENTRIES; 26: sup_loop_hafnian_complex_each, sup_gbs_sample; 25: sup_torontonian_table, sup_loop_torontonian_table, sup_mobius_subsets, SUP_TORONTONIAN_TABLE_MAX_N; 24: sup_loop_torontonian, sup_loop_torontonian_range, sup_loop_torontonian_plan, sup_ltor_exp, sup_ltor_exp_device, SUP_LOOP_TORONTONIAN_MAX_DEVICE_N; 23: sup_hafnian_complex_exact; 22: sup_torontonian, sup_torontonian_range, sup_torontonian_plan, SUP_TORONTONIAN_MAX_DEVICE_N; 21: sup_hafnian_complex_pt, sup_loop_hafnian_complex_pt, sup_hafnian_complex_pt_range, sup_hafnian_complex_pt_plan, SUP_HAFNIAN_PT_MAX_DEVICE_N; 20: sup_hafnian_complex, sup_loop_hafnian_complex, sup_hafnian_complex_plan; 19: sup_perman_complex_exact, sup_perman_complex_exact_range, SUP_CPLX_EXACT_MAX_DEVICE_N; 18: sup_perman_complex_quad, sup_perman_complex_quad_range, SUP_CPLX_QUAD_MAX_DEVICE_N; 17:sup_perman_complex_fock_minors, sup_perman_complex_fock_minors_plan, sup_boson_sample_fock; 16: sup_plan_census; 15: sup_perman_complex_minors, sup_perman_complex_minors_range, sup_boson_sample; 14: sup_perman_complex_fock, sup_perman_complex_fock_plan; 13: sup_perman_exact_range, sup_perman_quad_range, sup_perman_exact / sup_perman_quad report the walk that ran; 12: sup_perman_complex_batch, sup_perman_complex_submatrices; 11: sup_perman_complex, sup_perman_complex_range, sup_read_mtx_complex; 10: sup_opts.timing, sup_kernel_time (round 6); 9: sup_device_warmup, sup_opts.use_rccl = -1 (round 6); 8: sup_device_checks (round 5); 7: sup_rccl_devices, sup_stats.seg_cached_bits / seg_pair_bits */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SUP_OK            0
@@ -727,6 +727,36 @@ int sup_loop_hafnian_complex(const double* A, int M, const double* mu, const int
 /* The terms T of each matrix's sum, host only (no device).  terms may be NULL.
  * A null list or n outside [1, 64]: SUP_EINVAL.  Indices are only compared. */
 int sup_hafnian_complex_plan(const int32_t* idx, int n, uint64_t count, uint64_t* terms);
+
+/* Double-double hafnians and loop hafnians (ABI 29): the gathers, the sum, the
+ * layout, the slabs (SUP_HAFNIAN_SLAB) and the split over o->gpu_num devices of
+ * sup_hafnian_complex / sup_loop_hafnian_complex, with every running value a
+ * complex double-double (~106 bits per part; walk_hafdd.hip): the
+ * truth the fp64 hafnian entries are judged against on matrices that are not
+ * Gaussian integers.  The inputs are doubles; every weight prod C(s'_k, v_k) is
+ * converted from the exact integer, so groups of 58 and more copies keep the
+ * full precision.  out[4k .. 4k + 3] = re_hi, re_lo, im_hi, im_lo of result k,
+ * each (hi, lo) a normalised pair (hi = fl(hi + lo)); odd n without loop gives
+ * four exact zeros and walks nothing.  The error of hi + lo is bounded by a
+ * polynomial in n, Tw and K times 2^-103 times the sum of the 1-norms of the
+ * weighted terms (DESIGN.md 8q states it; tests/test_hafnian_quad.py asserts
+ * it).  A function of (A, mu, idx[k]) only: bit-identical on the device, on any
+ * device count, for any slab size and on host threads (on_cpu = 1).
+ * Checks, their order, errors and messages as sup_hafnian_complex (SUP_ENODEV
+ * without a device, no CPU fallback); n above SUP_HAFNIAN_QUAD_MAX_DEVICE_N,
+ * the largest order the device kernel serves with no scratch, no spilled VGPR
+ * and two waves per SIMD, with on_cpu = 0: SUP_EUNSUPPORTED on any machine,
+ * before the device is looked for (host threads serve n <= 64).
+ * st as sup_hafnian_complex's, with est_ops_per_step = the T-weighted mean of
+ *   hafdd_ops(W, n, loop) = 116 + g + 68 (floor(log2 m) + popcount(m) - 1)      plain, m = n / 2
+ *                         = 202 + g + (m ? 190 m - 68 : 0) + (n odd ? 68 : 0)   loop
+ * g = 72 for W <= 4 walk digits, else 180, in dd.hpp's nominal counts (dd_add
+ * 20, dd_add_d 9, dd_mul 7, cxdd_mul 68, cxdd_add 40). */
+#define SUP_HAFNIAN_QUAD_MAX_DEVICE_N 64
+int sup_hafnian_complex_quad(const double* A, int M, const int32_t* idx, int n, uint64_t count, const sup_opts* o,
+                             int on_cpu, double* out /* 4 per matrix */, sup_stats* st);
+int sup_loop_hafnian_complex_quad(const double* A, int M, const double* mu, const int32_t* idx, int n, uint64_t count,
+                                  const sup_opts* o, int on_cpu, double* out /* 4 per matrix */, sup_stats* st);
 
 /* Ragged loop hafnians with a displacement per item (ABI 26): the batch one
  * chain-rule step of a PNR Gaussian boson sampler needs.  A as above; mu holds

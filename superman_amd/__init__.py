@@ -24,6 +24,7 @@ __all__ = [
     "perman", "perman_cpu", "perman_exact", "perman_exact_range", "perman_quad", "perman_quad_range", "perman_complex", "perman_complex_range", "perman_complex_quad", "perman_complex_quad_range", "COMPLEX_QUAD_MAX_DEVICE_N", "perman_complex_exact", "perman_complex_exact_range", "COMPLEX_EXACT_MAX_DEVICE_N", "perman_complex_batch", "perman_complex_submatrices", "perman_complex_fock", "perman_complex_fock_plan", "perman_complex_fock_minors", "perman_complex_fock_minors_submatrices",
            "hafnian", "loop_hafnian", "hafnian_repeated", "hafnian_batch", "hafnian_plan",
            "hafnian_exact", "loop_hafnian_exact", "hafnian_exact_repeated", "hafnian_exact_batch",
+           "hafnian_quad", "loop_hafnian_quad", "hafnian_quad_repeated", "hafnian_quad_batch", "HAFNIAN_QUAD_MAX_DEVICE_N",
            "hafnian_powertrace", "loop_hafnian_powertrace", "hafnian_powertrace_batch", "hafnian_powertrace_range",
            "hafnian_powertrace_plan", "HAFNIAN_PT_MAX_DEVICE_N",
            "torontonian", "torontonian_batch", "torontonian_range", "torontonian_plan", "TORONTONIAN_MAX_DEVICE_N",
@@ -813,6 +814,67 @@ def hafnian_plan(idx):
     terms = np.zeros(max(count, 1), np.uint64)
     _lib.check(_lib.load().sup_hafnian_complex_plan(i32.ctypes.data, n, count, terms.ctypes.data), "hafnian_plan")
     return int(terms[0]) if single else terms[:count].copy()
+
+
+# include/superman.h SUP_HAFNIAN_QUAD_MAX_DEVICE_N: the largest order the device
+# kernel of hafnian_quad_batch serves (host threads serve n <= 64).
+HAFNIAN_QUAD_MAX_DEVICE_N = 64
+
+
+def hafnian_quad_batch(A, idx, mu=None, loop: bool = False, gpu_num: int = 1, device_id: int = 0, cpu: bool = False,
+                       threads: int = 16, return_stats: bool = False):
+    """``hafnian_batch`` in complex double-double (sup_hafnian_complex_quad,
+    sup_loop_hafnian_complex_quad): the same gathers, sum and layout, every
+    running value carried to ~106 bits per part (walk_hafdd.hip, or (cpu=True)
+    its host twin, bit-identical).  It is the truth ``hafnian``,
+    ``loop_hafnian`` and ``hafnian_powertrace`` are judged against on matrices
+    that are not Gaussian integers.  A list of shape [n] gives
+    ``((re_hi, re_lo), (im_hi, im_lo))``, of shape [count, n] a float64 array of
+    shape [count, 4] with those columns; each part is ``hi + lo`` exactly."""
+    a = np.ascontiguousarray(np.asarray(A, dtype=np.complex128))
+    if a.ndim != 2 or a.shape[0] != a.shape[1] or a.shape[0] < 1:
+        raise ValueError(f"expected a non-empty square matrix A, got shape {a.shape}")
+    i32, count, n, single = _haf_lists(idx)
+    lib = _lib.load()
+    o = _opts(gpu_num=gpu_num, device_id=device_id, threads=threads)
+    out, st = np.zeros(4 * max(count, 1)), SupStats()
+    if loop:
+        m = np.ascontiguousarray(np.diag(a) if mu is None else np.asarray(mu, dtype=np.complex128))
+        if m.shape != (a.shape[0],):
+            raise ValueError(f"mu must have shape [{a.shape[0]}], got {m.shape}")
+        rc = lib.sup_loop_hafnian_complex_quad(a.ctypes.data, a.shape[0], m.ctypes.data, i32.ctypes.data, n, count,
+                                               C.byref(o), int(bool(cpu)), out.ctypes.data, C.byref(st))
+    else:
+        rc = lib.sup_hafnian_complex_quad(a.ctypes.data, a.shape[0], i32.ctypes.data, n, count, C.byref(o),
+                                          int(bool(cpu)), out.ctypes.data, C.byref(st))
+    _lib.check(rc, "loop_hafnian_quad" if loop else "hafnian_quad")
+    v = out[:4 * count].reshape(count, 4).copy()
+    if single:
+        v = ((float(v[0, 0]), float(v[0, 1])), (float(v[0, 2]), float(v[0, 3])))
+    return (v, st.as_dict()) if return_stats else v
+
+
+def hafnian_quad(A, **kw):
+    """The hafnian of the whole complex symmetric matrix A in double-double
+    (``hafnian_quad_batch`` with idx = 0..n-1)."""
+    return hafnian_quad_batch(A, np.arange(np.shape(A)[0]), **kw)
+
+
+def loop_hafnian_quad(A, mu=None, **kw):
+    """The loop hafnian of the whole matrix A in double-double; ``mu``
+    defaults to its diagonal."""
+    return hafnian_quad_batch(A, np.arange(np.shape(A)[0]), mu=mu, loop=True, **kw)
+
+
+def hafnian_quad_repeated(A, rpt, mu=None, loop: bool = False, **kw):
+    """The double-double (loop) hafnian of A with mode k taken ``rpt[k]``
+    times (zeros allowed): ``hafnian_quad_batch`` on the list that repeats k
+    rpt[k] times."""
+    r = np.asarray(rpt)
+    if (r.ndim != 1 or r.shape[0] != np.shape(A)[0] or (r.size and not np.issubdtype(r.dtype, np.integer))
+            or (r < 0).any()):
+        raise ValueError(f"rpt must hold one non-negative integer per mode of A, got {rpt!r}")
+    return hafnian_quad_batch(A, np.repeat(np.arange(r.shape[0]), r), mu=mu, loop=loop, **kw)
 
 
 def _haf_exact_parts(x, what: str, name: str) -> np.ndarray:

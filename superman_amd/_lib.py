@@ -44,6 +44,7 @@ EXPORTS = [
     "sup_perman_complex_minors", "sup_perman_complex_minors_range", "sup_boson_sample",
     "sup_perman_complex_fock_minors", "sup_perman_complex_fock_minors_plan", "sup_boson_sample_fock",
     "sup_hafnian_complex", "sup_loop_hafnian_complex", "sup_hafnian_complex_plan", "sup_hafnian_complex_exact",
+    "sup_hafnian_complex_quad", "sup_loop_hafnian_complex_quad",
     "sup_loop_hafnian_complex_each", "sup_gbs_sample", "sup_loop_torontonian_each", "sup_threshold_sample",
     "sup_loop_hafnian_table", "sup_loop_hafnian_table_plan",
     "sup_hafnian_complex_pt", "sup_loop_hafnian_complex_pt", "sup_hafnian_complex_pt_range", "sup_hafnian_complex_pt_plan",
@@ -144,7 +145,7 @@ def load() -> C.CDLL:
             build()
         lib = C.CDLL(LIB_PATH)
         _declare(lib)
-        if lib.sup_abi_version() != 28:
+        if lib.sup_abi_version() != 29:
             raise RuntimeError("libsuperman_hip.so ABI version mismatch")
         _lib = lib
         return lib
@@ -202,6 +203,9 @@ def _declare(lib: C.CDLL) -> None:
     lib.sup_hafnian_complex.argtypes = [P, I, P, I, C.c_uint64, C.POINTER(SupOpts), I, P, C.POINTER(SupStats)]
     lib.sup_loop_hafnian_complex.argtypes = [P, I, P, P, I, C.c_uint64, C.POINTER(SupOpts), I, P, C.POINTER(SupStats)]
     lib.sup_hafnian_complex_plan.argtypes = [P, I, C.c_uint64, P]
+    lib.sup_hafnian_complex_quad.argtypes = [P, I, P, I, C.c_uint64, C.POINTER(SupOpts), I, P, C.POINTER(SupStats)]
+    lib.sup_loop_hafnian_complex_quad.argtypes = [P, I, P, P, I, C.c_uint64, C.POINTER(SupOpts), I, P,
+                                                  C.POINTER(SupStats)]
     lib.sup_loop_hafnian_complex_each.argtypes = [P, I, P, C.c_uint64, P, P, I, P, C.c_uint64, C.POINTER(SupOpts), I, P,
                                                   C.POINTER(SupStats)]
     lib.sup_gbs_sample.argtypes = [P, I, P, P, I, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(SupOpts), I, P,

@@ -9,6 +9,7 @@
 #include "engine.hpp"
 #include "hafnian_exact.hpp"
 #include "hafnian_pt.hpp"
+#include "hafnian_quad.hpp"
 #include "loop_torontonian.hpp"
 #include "torontonian.hpp"
 #include "lhaf_table.hpp"
@@ -654,6 +655,43 @@ int sup_loop_hafnian_complex(const double* A, int M, const double* mu, const int
   HafIn in;
   in.A = A, in.M = M, in.mu = mu, in.idx = idx, in.loop = true;
   return hafnian_entry(in, n, count, o, on_cpu, out, st);
+}
+
+static int hafnian_quad_entry(const HafIn& in, int n, uint64_t count, const sup_opts* o_in, int on_cpu, double* out,
+                              sup_stats* st) {
+  auto t0 = std::chrono::steady_clock::now();
+  sup_opts o;
+  if (o_in) o = *o_in;
+  else sup_opts_init(&o);
+  HafInfo hi;
+  if (int rc = hafnian_quad(in, n, count, o, on_cpu != 0, out, &hi)) return rc;
+  if (st) {
+    std::memset(st, 0, sizeof(*st));
+    st->kernel_ms = hi.kernel_ms;
+    st->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    st->gray_steps = count << (n - 1);  // nominal: the sum without repeats
+    st->visited_steps = hi.terms;
+    st->devices_used = hi.devices;
+    st->grid = hi.grid;
+    st->walk_kind = (int)kWalkDense;
+    st->leaves = (int)std::min<uint64_t>(count, 0x7fffffffu);
+    st->est_ops_per_step = hi.ops;
+  }
+  return SUP_OK;
+}
+
+int sup_hafnian_complex_quad(const double* A, int M, const int32_t* idx, int n, uint64_t count, const sup_opts* o,
+                             int on_cpu, double* out, sup_stats* st) {
+  HafIn in;
+  in.A = A, in.M = M, in.idx = idx;
+  return hafnian_quad_entry(in, n, count, o, on_cpu, out, st);
+}
+
+int sup_loop_hafnian_complex_quad(const double* A, int M, const double* mu, const int32_t* idx, int n, uint64_t count,
+                                  const sup_opts* o, int on_cpu, double* out, sup_stats* st) {
+  HafIn in;
+  in.A = A, in.M = M, in.mu = mu, in.idx = idx, in.loop = true;
+  return hafnian_quad_entry(in, n, count, o, on_cpu, out, st);
 }
 
 int sup_hafnian_complex_plan(const int32_t* idx, int n, uint64_t count, uint64_t* terms) {

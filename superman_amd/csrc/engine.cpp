@@ -5,6 +5,7 @@
 #include "engine.hpp"
 #include "hafnian_exact.hpp"
 #include "hafnian_pt.hpp"
+#include "hafnian_quad.hpp"
 #include "lhaf_table.hpp"
 #include "loop_torontonian.hpp"
 #include "torontonian.hpp"
@@ -1505,6 +1506,90 @@ int run_hafnian(int dev, const HafSlab& S, const HafIn& in, double* out, double*
   SUP_HIP(launch_haf_fold(c->d_chunk, p.mats, K, S.div, c->d_cbout, s));
   SUP_HIP(hipEventRecord(c->ev1, s));
   SUP_HIP(hipMemcpyAsync(out, c->d_cbout, (size_t)(K * 2) * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (grid_out) *grid_out = (int)geo.grid;
+  return timed_sync(c, kernel_ms);
+}
+
+// Double-double hafnian walk (walk_hafdd.hip) of slab S on device `dev`, as
+// run_hafnian's: A, mu and the slab's descriptor pools (the dd program, the dd
+// weight triangle, the dd coefficients) go up, then prepare, the walk over the
+// slab's queue and the per-matrix fold run on the context's stream, and one
+// download brings 32 bytes per matrix into out.  The buffers are the
+// collision-aware walk's (same context lock).
+int run_hafnian_quad(int dev, const HafddSlab& S, const HafIn& in, double* out, double* kernel_ms, int* grid_out) {
+  if (kernel_ms) *kernel_ms = 0.0;
+  if (grid_out) *grid_out = 0;
+  const uint64_t K = S.mats.size(), chunks = S.chunks.size();
+  if (K == 0) return SUP_OK;
+  const bool shape_ok = S.n >= 1 && S.n <= SUP_MAX_N && (S.loop || !(S.n & 1)) &&
+                        (!S.loop || S.coef.size() == 2 * ((size_t)S.n / 2 + 1));
+  if (!shape_ok || chunks == 0 || chunks > 0x7fffffffull || !out || !in.A || in.M < 1 || (S.loop && !in.mu)) {
+    set_error("run_hafnian_quad: bad request");
+    return SUP_EINVAL;
+  }
+  const std::vector<double>& wts = hafdd_weights();
+  // the packed pools, each starting on a 16-byte unit (the program first: its entries are read 16 bytes at a time)
+  auto units = [](size_t bytes) { return (bytes + 15) / 16; };
+  const size_t u_prog = 0, u_dig = u_prog + units(S.prog.size() * sizeof(HafddStep));
+  const size_t u_mats = u_dig + units(S.dig.size() * sizeof(HafDigit));
+  const size_t u_chunks = u_mats + units(K * sizeof(HafMat));
+  const size_t u_wts = u_chunks + units(chunks * sizeof(FockChunk));
+  const size_t u_grp = u_wts + units(wts.size() * sizeof(double));
+  const size_t u_coef = u_grp + units(S.grp.size() * sizeof(int32_t));
+  const size_t u_end = u_coef + units(S.coef.size() * sizeof(double)) + 1;
+  const size_t a_doubles = (size_t)2 * in.M * in.M;
+  const size_t mu_doubles = S.loop ? (size_t)2 * in.M : 0;
+  CtxGuard guard;
+  int rc = guard.open(dev, "device buffers");
+  if (rc) return rc;
+  DeviceCtx* c = guard.c;
+  int occ = 0;
+  SUP_HIP(hafdd_occupancy(S.loop, &occ));
+  if ((rc = ensure(c->d_cbtab, c->cbtab_cap, (size_t)S.tab_doubles))) return rc;
+  if ((rc = ensure(c->d_cbU, c->cbU_cap, a_doubles + mu_doubles))) return rc;
+  if ((rc = ensure(c->d_chunk, c->chunk_cap, (size_t)(4 * chunks)))) return rc;
+  if ((rc = ensure(c->d_cbout, c->cbout_cap, (size_t)(K * 4)))) return rc;
+  if ((rc = ensure(c->d_fock, c->fock_cap, u_end))) return rc;
+  hipStream_t s = c->stream;
+  c->tables_uid = 0;  // the walk leaves head 0 nonzero
+  c->head_zero[0] = false;
+  auto up = [&](void* dst, const void* src, size_t bytes) {
+    return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+  };
+  SUP_HIP(up(c->d_cbU, in.A, a_doubles * sizeof(double)));
+  SUP_HIP(up(c->d_cbU + a_doubles, in.mu, mu_doubles * sizeof(double)));
+  SUP_HIP(up(c->d_fock + u_grp, S.grp.data(), S.grp.size() * sizeof(int32_t)));
+  SUP_HIP(up(c->d_fock + u_prog, S.prog.data(), S.prog.size() * sizeof(HafddStep)));
+  SUP_HIP(up(c->d_fock + u_dig, S.dig.data(), S.dig.size() * sizeof(HafDigit)));
+  SUP_HIP(up(c->d_fock + u_mats, S.mats.data(), K * sizeof(HafMat)));
+  SUP_HIP(up(c->d_fock + u_chunks, S.chunks.data(), chunks * sizeof(FockChunk)));
+  SUP_HIP(up(c->d_fock + u_wts, wts.data(), wts.size() * sizeof(double)));
+  SUP_HIP(up(c->d_fock + u_coef, S.coef.data(), S.coef.size() * sizeof(double)));
+  SUP_HIP(hipMemsetAsync(c->d_counter, 0, sizeof(unsigned), s));
+  const uint64_t resident = (uint64_t)c->cus * (uint64_t)std::max(occ, 1);
+  const char* fg = std::getenv("SUP_WALK_GROUP");  // tests, read per call: chunks per ticket (the bits do not change)
+  const LaunchGeom geo = walk_geometry(chunks, resident, kWavesPerBlock, false, fg ? std::max(1, std::atoi(fg)) : 0);
+  HafddParams p{};
+  p.tabs = c->d_cbtab;
+  p.prog = reinterpret_cast<const HafddStep*>(c->d_fock + u_prog);
+  p.dig = reinterpret_cast<const HafDigit*>(c->d_fock + u_dig);
+  p.mats = reinterpret_cast<const HafMat*>(c->d_fock + u_mats);
+  p.chunks = reinterpret_cast<const FockChunk*>(c->d_fock + u_chunks);
+  p.wts = reinterpret_cast<const double*>(c->d_fock + u_wts);
+  p.coef = reinterpret_cast<const double*>(c->d_fock + u_coef);
+  p.chunk_count = chunks;
+  p.chunk_out = c->d_chunk;
+  p.counter = c->d_counter;
+  p.group = geo.group;
+  p.n = (unsigned)S.n;
+  SUP_HIP(hipEventRecord(c->ev0, s));
+  SUP_ON_DEVICE(c->dev, "double-double hafnian walk launch");
+  SUP_HIP(launch_hafdd_prepare(c->d_cbU, in.M, S.loop ? c->d_cbU + a_doubles : nullptr,
+                               reinterpret_cast<const int32_t*>(c->d_fock + u_grp), p.mats, K, c->d_cbtab, s));
+  SUP_HIP(launch_hafdd(S.loop, p, (int)geo.grid, s));
+  SUP_HIP(launch_hafdd_fold(c->d_chunk, p.mats, K, S.div.hi, S.div.lo, S.loop, c->d_cbout, s));
+  SUP_HIP(hipEventRecord(c->ev1, s));
+  SUP_HIP(hipMemcpyAsync(out, c->d_cbout, (size_t)(K * 4) * sizeof(double), hipMemcpyDeviceToHost, s));
   if (grid_out) *grid_out = (int)geo.grid;
   return timed_sync(c, kernel_ms);
 }

@@ -49,6 +49,11 @@
 // are integers, through sup_hafnian_complex_exact (residue walk and CRT, -g or
 // -c, n <= 64); prints "Hafnian (exact): <re> <im>", two decimal integers.
 // Refused with --powertrace.
+// --hafnian --quad [--loop] [--rpt ...]: the same value in complex double-double
+// through sup_hafnian_complex_quad / sup_loop_hafnian_complex_quad (-g or -c);
+// prints "Hafnian (double-double): <re_hi> <re_lo> <im_hi> <im_lo>".  Only the
+// long spelling selects it (-q beside --hafnian stays refused); refused with
+// --powertrace and with --exact.
 // --torontonian [--modes 0,3,5]: sup_torontonian of a 2M x 2M Hermitian
 // MatrixMarket `complex` file (thewalrus' ordering) on the listed distinct
 // modes (default: all M); prints "Torontonian: <value>".  -g the device
@@ -81,7 +86,7 @@ struct Cli {
   bool generic = true, dense = true, approximation = false, gpu = false, cpu = false, grid_graph = false;
   bool rccl = false, verbose = false, compression = false, exact = false, quad = false;
   bool half_calc = false, half_store = false, complex = false, complex_quad = false, complex_exact = false, preprocessing_given = false, gpu_num_given = false;
-  bool hafnian = false, loop = false, powertrace = false, torontonian = false, table = false, raw = false;
+  bool hafnian = false, hafnian_quad = false, quad_long = false, loop = false, powertrace = false, torontonian = false, table = false, raw = false;
   int gpu_num = 2, threads = 16, perman_algo = 1, preprocessing = 0, device = 0, reps = 1;
   double scaling = -1.0;
   long number_of_times = 100000;  // main.cu:338-344 defaults
@@ -249,6 +254,14 @@ int run_hafnian_cli(const Cli& c) {
     std::fprintf(stderr, "perman: --hafnian --exact does not combine with --powertrace\n");
     return 1;
   }
+  if (c.hafnian_quad && c.powertrace) {
+    std::fprintf(stderr, "perman: --hafnian --quad does not combine with --powertrace\n");
+    return 1;
+  }
+  if (c.hafnian_quad && c.exact) {
+    std::fprintf(stderr, "perman: --hafnian --quad does not combine with --exact\n");
+    return 1;
+  }
   double* mat = nullptr;
   int M = 0, nnz = 0;
   if (sup_read_mtx_complex(c.filename.c_str(), &mat, &M, &nnz) != SUP_OK) return fail("reading complex matrix");
@@ -282,6 +295,7 @@ int run_hafnian_cli(const Cli& c) {
   o.device_id = c.device;
   o.threads = c.threads;
   double out[2] = {0.0, 0.0};
+  double q[4] = {0.0, 0.0, 0.0, 0.0};   // --quad: re_hi, re_lo, im_hi, im_lo
   char xre[768] = "0", xim[768] = "0";  // --exact: decimal integers
   sup_stats st;
   int rc = SUP_OK;
@@ -290,6 +304,9 @@ int run_hafnian_cli(const Cli& c) {
     if (c.exact)
       rc = sup_hafnian_complex_exact(mat, M, c.loop ? mu.data() : nullptr, idx.data(), (int)idx.size(), 1, &o,
                                      c.gpu ? 0 : 1, xre, xim, sizeof(xre), &st);
+    else if (c.hafnian_quad)
+      rc = c.loop ? sup_loop_hafnian_complex_quad(mat, M, mu.data(), idx.data(), (int)idx.size(), 1, &o, c.gpu ? 0 : 1, q, &st)
+                  : sup_hafnian_complex_quad(mat, M, idx.data(), (int)idx.size(), 1, &o, c.gpu ? 0 : 1, q, &st);
     else if (c.powertrace)
       rc = c.loop ? sup_loop_hafnian_complex_pt(mat, M, mu.data(), idx.data(), (int)idx.size(), 1, &o, c.gpu ? 0 : 1, out, &st)
                   : sup_hafnian_complex_pt(mat, M, idx.data(), (int)idx.size(), 1, &o, c.gpu ? 0 : 1, out, &st);
@@ -298,12 +315,18 @@ int run_hafnian_cli(const Cli& c) {
                   : sup_hafnian_complex(mat, M, idx.data(), (int)idx.size(), 1, &o, c.gpu ? 0 : 1, out, &st);
   const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / (double)c.reps;
   sup_free(mat);
-  if (rc != SUP_OK) return fail(c.exact ? (c.loop ? "exact loop hafnian" : "exact hafnian") : c.loop ? "loop hafnian" : "hafnian");
+  if (rc != SUP_OK)
+    return fail(c.exact          ? (c.loop ? "exact loop hafnian" : "exact hafnian")
+                : c.hafnian_quad ? (c.loop ? "double-double loop hafnian" : "double-double hafnian")
+                : c.loop         ? "loop hafnian"
+                                 : "hafnian");
+  if (c.hafnian_quad) out[0] = q[0], out[1] = q[2];
   if (c.exact) out[0] = std::strtod(xre, nullptr), out[1] = std::strtod(xim, nullptr);
   std::cout << "Result: " << (c.gpu ? "gpu_" : "cpu_") << (c.loop ? "loop_hafnian64_complex" : "hafnian64_complex")
-            << (c.powertrace ? "_powertrace" : "") << (c.exact ? "_exact" : "") << " "
+            << (c.powertrace ? "_powertrace" : "") << (c.exact ? "_exact" : "") << (c.hafnian_quad ? "_quad" : "") << " "
             << out[0] << " " << out[1] << " in " << sec << std::endl;
   if (c.exact) std::printf("Hafnian (exact): %s %s\n", xre, xim);
+  else if (c.hafnian_quad) std::printf("Hafnian (double-double): %.17e %.17e %.17e %.17e\n", q[0], q[1], q[2], q[3]);
   else std::printf("Hafnian: %.17e %.17e\n", out[0], out[1]);
   if (c.verbose)
     std::printf("Stats: devices %d kernel_ms %.3f wall_ms %.3f terms %llu grid %d\n", st.devices_used, st.kernel_ms,
@@ -482,7 +505,7 @@ int main(int argc, char** argv) {
                                         {"rccl", 0, NULL, 'R'},          {"verbose", 0, NULL, 'v'},
                                         {"compression", 0, NULL, 'o'},   {"scaling", 1, NULL, 'u'},
                                         {"seed", 1, NULL, 'S'},          {"jit", 1, NULL, 'J'},
-                                        {"exact", 0, NULL, 'E'},         {"quad", 0, NULL, 'q'},
+                                        {"exact", 0, NULL, 'E'},         {"quad", 0, NULL, 1012},
                                         {"halfCalc", 0, NULL, 'h'},      {"halfStore", 0, NULL, 'w'},
                                         {"gridMultip", 1, NULL, 'e'},    {"checkpoint", 1, NULL, 'C'},
                                         {"complex", 0, NULL, 1000},
@@ -544,6 +567,7 @@ int main(int argc, char** argv) {
       case 1009: c.gamma = optarg; break;
       case 1010: c.table = true; break;
       case 1011: c.raw = true; break;
+      case 1012: c.quad_long = true; break;
       case 'v': c.verbose = true; break;
       // v2 flags (revised_perman/main.cpp:1431-1460): -w stores the matrix in
       // single precision (the permanent of the float-rounded entries); -h asks
@@ -571,6 +595,8 @@ int main(int argc, char** argv) {
   }
   for (int i = optind; i < argc; ++i) std::printf("Non-option argument %s\n", argv[i]);
   if (!c.cpu && !c.gpu) c.gpu = true;  // main.cu:482-484
+  // --quad is -q, except beside --hafnian, where it asks for the double-double hafnian
+  if (c.quad_long) (c.hafnian && !c.torontonian ? c.hafnian_quad : c.quad) = true;
   if (c.torontonian) return run_torontonian_cli(c);
   if (c.table || c.raw) {
     std::fprintf(stderr, "perman: --table and --raw go with --torontonian\n");
